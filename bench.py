@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the HIP render loop (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+--dump-outputs DIR then also writes the last timed step's frame (DIR/frame.npy)
+and the last timed launch's ray counts (DIR/ray_counts.npy).  Every other
+measurement and check listed under "Also reported" runs only with --full.
 
 A step renders ONE frame of the workload: each rank traces its cyclic 8-row
 bands through librt_hip.so (on torch's current stream, output resident in
@@ -15,7 +20,9 @@ gather.  Every frame is rendered and delivered in full.  Total work per step is 
 as N grows ("scaling": "strong").  value = rays of the frame x K / max-over-ranks wall
 time of the K timed steps.
 
-Also reported:
+Also reported (roofline and hbm_write in every run: they reuse the timed
+launches' kernel times; the others, the untimed golden / reassembly checks and
+the gather time of N > 1 only with --full):
   roofline      fp64 VALU roof of the render kernels (render_kernel +
                 render_deferred): the fp64 FLOPs they EXECUTE per frame (rocprofv3
                 PMC: 64 x (ADD + MUL + 2 FMA + TRANS)_F64 wave-instructions,
@@ -355,8 +362,32 @@ def golden_check(torch, workload, depth, shards, launches, image, rank):
             "what": "every frame of the last timed launch" if image is None else "rank 0's last reassembled frame"}
 
 
+DUMP_MAX_ELEMS = 8 << 20  # float32 elements of a dumped frame (32 MiB); a larger frame is sampled
+DUMP_SEED = 420
+
+
+def dump_outputs(dirname, frame, st):
+    """--dump-outputs: what a caller of the timed path received from its last
+    step.  frame.npy: the last timed frame (rank 0's reassembled one for N > 1),
+    [H, W, 3] RGB8 values as float32; a frame above DUMP_MAX_ELEMS values is
+    written as the 1-D sample of DUMP_MAX_ELEMS of them at sorted flat indices
+    drawn without replacement by numpy's default_rng(DUMP_SEED).
+    ray_counts.npy: float64 [primary, shadow, reflect] of the last timed launch
+    (all its frames, this rank's rows)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    a = frame.cpu().numpy()
+    if a.size > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(dirname, "frame.npy"), a.astype(np.float32))
+    np.save(os.path.join(dirname, "ray_counts.npy"),
+            np.array([st.rays_primary, st.rays_shadow, st.rays_reflect], dtype=np.float64))
+
+
 def measure(rt_hip, torch, dist, workload, steps, warmup, world, rank, device, cull=True, batch=4, dist_on=None,
-            depth=None, extras=False):
+            depth=None, extras=False, full_run=True, dump=None):
     import rt_frames
 
     if dist_on is None:
@@ -498,10 +529,16 @@ def measure(rt_hip, torch, dist, workload, steps, warmup, world, rank, device, c
         frame_rays = my_rays
         rank_kernel_ms = [round(kframe, 5)]
         seen_world = 1
-    golden = golden_check(torch, workload, depth, shards, rt_frames.batch_sizes(steps, F), image if dist_on else None,
-                          rank)
+    launches = rt_frames.batch_sizes(steps, F)
+    if dump and rank == 0 and launches:
+        # untimed: the last timed step's frame, before any later launch writes the shard buffers again
+        last = image if dist_on else shards[(len(launches) - 1) & 1][launches[-1] - 1]
+        dump_outputs(dump, last, r.stats())
+    golden = None
+    if full_run:
+        golden = golden_check(torch, workload, depth, shards, launches, image if dist_on else None, rank)
     assembled_ok = None
-    if dist_on and rank == 0 and steps > 0:
+    if full_run and dist_on and rank == 0 and steps > 0:
         # untimed: the last frame reassembled from the gathered shards must equal
         # one full-frame render on this device, byte for byte
         full = torch.empty((H, W, 3), dtype=torch.uint8, device=f"cuda:{device}")
@@ -535,7 +572,7 @@ def measure(rt_hip, torch, dist, workload, steps, warmup, world, rank, device, c
         extra["single_frame"] = single_frame(rt_hip, r, cam, W, H, D, rows, shards[0][0].data_ptr())
         extra["moving_camera"] = moving_camera(rt_hip, torch, r, cam, W, H, D, rows, shards[0], F)
     gather_ms = None
-    if dist_on and steps > 0:
+    if full_run and dist_on and steps > 0:
         # untimed: one batch's RCCL gather to rank 0 alone ("plus the
         # gather time"), mean of 5, in-stream events around the collective
         dist.barrier()
@@ -567,10 +604,20 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--workload", default="synth200_1920x1080_d4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the complex.txt north-star line item")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check: the CPU baselines, the "
+                         "complex.txt north-star line item, the single-frame, moving-camera and end-to-end line "
+                         "items, the golden-image check and, on the N > 1 data path, the reassembly check and the "
+                         "gather time (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's frame as DIR/frame.npy (float32 RGB "
+                         "values, [H, W, 3]; a fixed seeded sample of a frame above 8 Mi values) and the last timed "
+                         "launch's ray counts as DIR/ray_counts.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true",
+                    help="with --full: skip the complex.txt north-star line item")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the single-frame, moving-camera and end-to-end line items (N = 1 only)")
+                    help="with --full: skip the single-frame, moving-camera and end-to-end line items (N = 1 only)")
     ap.add_argument("--frames-per-launch", "--frames-per-gather", dest="frames_per_launch", type=int, default=32,
                     help="frames rendered by one kernel launch (rt_render_frames_async, 1..32); for N > 1 also "
                          "the frames per RCCL gather to rank 0 (one collective per batch)")
@@ -583,6 +630,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no external launcher: start the ranks here, before anything loads torch
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -614,11 +663,11 @@ def main():
 
     cull = not args.brute_force
     batch = max(1, min(rt_hip.MAX_FRAMES, args.frames_per_launch))
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
     m = measure(rt_hip, torch, dist, args.workload, args.steps, args.warmup, world, rank, local, cull, batch, dist_on,
-                args.depth, extras)
+                args.depth, extras, full_run=args.full, dump=args.dump_outputs)
     also = {}
-    if not args.no_also and args.workload != "complex_1920x1080_d4":
+    if args.full and not args.no_also and args.workload != "complex_1920x1080_d4":
         a = measure(rt_hip, torch, dist, "complex_1920x1080_d4", max(args.steps // 2, 5), 2, world, rank, local,
                     cull, batch, dist_on, extras=extras)
         also["complex_1920x1080_d4"] = {
@@ -781,7 +830,7 @@ def main():
                 line[k] = m[k]
         if e2e:
             line["e2e"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(m["scene_file"], m["W"], m["H"], m["D"], m["frame_rays"])
             # ray_openmp's loop on the host cores this job may use (16 on the GPU box)
             line["cpu_baseline_all_cores"] = cpu_baseline(m["scene_file"], m["W"], m["H"], m["D"],

@@ -18,7 +18,7 @@ done
 for rep in 1 2; do
   for v in cur ${VARIANTS:-lifo compact lifocompact}; do
     if [ $v = cur ]; then unset RT_HIP_LIB; else export RT_HIP_LIB=$ROOT/cs420-ray-tracer_amd/variants/exp/librt_hip_$v.so; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras --steps 64 --warmup 16 > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err || exit 2
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras --steps 64 --warmup 16 > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err || exit 2
     python -c "
 import json; d=json.loads(open('$OUT/bench_${v}_$rep.json').read().strip().splitlines()[-1]); a=d['also'].get('complex_1920x1080_d4',{})
 print('%-12s %9.1f Mrays/s k=%.4f ms/frame | complex k=%.4f' % ('$v', d['value'], d['roofline']['kernel_ms_per_frame'], a.get('kernel_ms_per_frame',0)))"

@@ -17,7 +17,7 @@ for rep in $(seq 1 "$REPS"); do
     lib="${spec%%@*}"; knobs=""; [ "$spec" != "$lib" ] && knobs="${spec#*@}"
     if [ "$lib" = cur ]; then unset RT_HIP_LIB; else export RT_HIP_LIB="$ROOT/$lib"; fi
     out="gpurun_out/${TAG}_$(basename "$lib" .so)$(echo "$knobs" | tr '@=' '__')_$rep"
-    timeout -k 10 300 env $(echo "$knobs" | tr '@' ' ') python bench.py --no-cpu-baseline --workload "$W" --steps 64 ${BENCH_ARGS} > "$out.json" 2> "$out.err"; rc=$?
+    timeout -k 10 300 env $(echo "$knobs" | tr '@' ' ') python bench.py --full --no-cpu-baseline --workload "$W" --steps 64 ${BENCH_ARGS} > "$out.json" 2> "$out.err"; rc=$?
     [ $rc -eq 0 ] || { echo "$lib rc=$rc"; tail -5 "$out.err"; exit $rc; }
     python -c "
 import json; d=json.load(open('$out.json')); a=d['also'].get('complex_1920x1080_d4',{})

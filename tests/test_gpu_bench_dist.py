@@ -16,8 +16,8 @@ from conftest import REPO
 @pytest.mark.parametrize("batch", ["1", "4", "16"])
 def test_bench_force_dist_reassembles_frame(batch):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29540 + int(batch)))
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-dist", "--no-cpu-baseline",
-                          "--no-also", "--steps", "7", "--warmup", "1", "--frames-per-launch", batch,
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-dist", "--full",
+                          "--no-cpu-baseline", "--no-also", "--steps", "7", "--warmup", "1", "--frames-per-launch", batch,
                           "--workload", "medium_1920x1080_d2"],
                          capture_output=True, text=True, timeout=150, env=env, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -38,8 +38,8 @@ def test_bench_gpus2_launches_ranks_or_fails_fast():
     import torch
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--no-cpu-baseline",
-                          "--no-also", "--steps", "4", "--warmup", "1", "--frames-per-launch", "2",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full",
+                          "--no-cpu-baseline", "--no-also", "--steps", "4", "--warmup", "1", "--frames-per-launch", "2",
                           "--workload", "medium_1920x1080_d2"],
                          capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
     if torch.cuda.device_count() < 2:
