@@ -1832,29 +1832,125 @@ using namespace rtk;
 constexpr int kBvhAlwaysAbove = 1024;
 constexpr size_t kUgMaxEntries = size_t(64) << 20;  // behind-grid list entries (20 B each)
 
+// The one owner of an allocation: move-only, freed exactly once.  bytes() is
+// the size asked for (a 0-byte request still allocates, so get() is never
+// null after a successful alloc).
+template <class T, class Alloc>
+class OwnedBuf {
+ public:
+  OwnedBuf() = default;
+  OwnedBuf(OwnedBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+  OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, bytes_ = o.bytes_;
+      o.p_ = nullptr, o.bytes_ = 0;
+    }
+    return *this;
+  }
+  ~OwnedBuf() { reset(); }
+  T *get() const { return p_; }
+  size_t bytes() const { return bytes_; }
+  void reset() {
+    if (p_) Alloc::release(p_);
+    p_ = nullptr;
+    bytes_ = 0;
+  }
+  hipError_t alloc(size_t bytes) {
+    reset();
+    void *q = nullptr;
+    const hipError_t e = Alloc::acquire(&q, bytes ? bytes : 1);
+    if (e == hipSuccess) p_ = static_cast<T *>(q), bytes_ = bytes;
+    return e;
+  }
+
+ private:
+  T *p_ = nullptr;
+  size_t bytes_ = 0;
+};
+struct DevAlloc {
+  static hipError_t acquire(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void release(void *p) { (void)hipFree(p); }
+};
+struct PinnedAlloc {
+  static hipError_t acquire(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void release(void *p) { (void)hipHostFree(p); }
+};
+template <class T>
+using PinnedBuf = OwnedBuf<T, PinnedAlloc>;
+template <class T>
+struct DevBuf : OwnedBuf<T, DevAlloc> {
+  // room for v.size() + pad elements, the first v.size() of them copied from v
+  hipError_t upload(const std::vector<T> &v, size_t pad = 0) {
+    const hipError_t e = this->alloc(sizeof(T) * (v.size() + pad));
+    if (e != hipSuccess || v.empty()) return e;
+    return hipMemcpy(this->get(), v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+  }
+};
+
+// What rt_upload_scene builds and free_scene releases: the scene's device
+// arrays with their sizes, and the flags saying which of them a launch may use.
+struct Scene {
+  bool has_scene = false;
+  DevBuf<SphGeo> geo;
+  DevBuf<double> rad;  // |radius|, for the conservative cull only
+  DevBuf<SphMat> mat;
+  DevBuf<LightD> lights;
+  int nsph = 0, nlight = 0;
+  double amb[3] = {0, 0, 0};
+  double c0[3] = {0, 0, 0};
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // bounds of spheres and lights
+  double rmax = 0;
+  std::vector<SchedSphere> refl;  // reflective spheres of the scene (rt_sched.h)
+  // BVH over the spheres (fallback for incoherent groups)
+  DevBuf<BvhNode> bvh;
+  DevBuf<int32_t> prims;
+  DevBuf<float4> pf;
+  DevBuf<BvhNode2> bvh2;
+  DevBuf<BvhNode4> bvh4;  // 4-wide nodes for the ordered walk (RT_HIP_BVH4=0: two-child walk)
+  int bvh2_root = -1, bvh_depth = 0, bvh4_root = -1, bvh4_stack = 0;
+  int bvh_nodes = 0;
+  int bvh2_nodes = 0, bvh4_nodes = 0, bvh_prims = 0;  // sizes the RT_CHECK build checks node / leaf indices against
+  // per-light direction grids for shadow rays (rt_lightgrid.h)
+  DevBuf<int32_t> lg_start, lg_ids;
+  long long lg_nstart = 0, lg_nids = 0;
+  // sphere grids (rt_lightgrid.h build_sphere_grids): the closest hit of
+  // reflection rays in the kFast kernels, for the reflective spheres
+  DevBuf<int32_t> sg_start;
+  DevBuf<int2> sg_ent;  // (sphere, tlo bits)
+  DevBuf<double> sg_rho2;
+  int sg_n = 0, sg_grids = 0;
+  long long sg_nstart = 0, sg_nent = 0;
+  bool sg_ok = false;
+  size_t sg_entries = 0;
+  // RT_HIP_SPHERE_GRID auto: the grids are built by the scene's first launch
+  // of more than one frame, or its second launch -- not by rt_upload_scene: a
+  // one-image render (the drop-in ray_serial) spends ~1.8 ms building 143
+  // grids (synth200) that save it ~0.05 ms of kernel time
+  std::vector<rt_sphere> sg_src;  // the uploaded spheres, held only until sphere_grids has run
+  double sg_diam = 0.0;
+  bool sg_pending = false;
+  long long launches = 0;  // render launches since the scene was uploaded
+  // behind grid (rt_bvh.h build_ugrid): the backward half of the ordered
+  // walks' closest-hit lines (rt_device.h behind_cells)
+  DevBuf<int32_t> ug_rid, ug_ids, ug_glob;
+  DevBuf<UgRec> ug_rec, ug_q;
+  UgArgs ug{};  // its device arguments (on = 0 until a launch allows it)
+  float ug_reg_margin = 0.0f, ug_extent = 0.0f;
+  bool ug_ok = false;
+  size_t ug_entries = 0;
+};
+
 struct rt_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t switch_ev = nullptr;  // rt_set_stream: orders the new stream after the old one
-  SphGeo *d_geo = nullptr;
-  double *d_rad = nullptr;  // |radius|, for the conservative cull only
-  SphMat *d_mat = nullptr;
+  Scene scene;
   bool cull = true;
-  // BVH over the spheres (fallback for incoherent groups), built at upload
-  BvhNode *d_bvh = nullptr;
-  int32_t *d_prims = nullptr;
-  float4 *d_pf = nullptr;
-  BvhNode2 *d_bvh2 = nullptr;
-  int bvh2_root = -1, bvh_depth = 0, bvh_ordered = 1;  // RT_HIP_BVH_ORDERED
-  BvhNode4 *d_bvh4 = nullptr;  // 4-wide nodes for the ordered walk (RT_HIP_BVH4=0: two-child walk)
-  int bvh4_root = -1, bvh4_stack = 0, bvh_wide = 1;
-  int bvh_nodes = 0;
-  int bvh2_nodes = 0, bvh4_nodes = 0, bvh_prims = 0;  // sizes the RT_CHECK build checks node / leaf indices against
-  // per-light direction grids for shadow rays (rt_lightgrid.h), built at upload
-  int32_t *d_lg_start = nullptr, *d_lg_ids = nullptr;
+  int bvh_ordered = 1;  // RT_HIP_BVH_ORDERED
+  int bvh_wide = 1;     // RT_HIP_BVH4
   int lg_n = 128, lg_on = 1;  // lg_n: the grid of the uploaded scene
-  long long lg_nstart = 0, lg_nids = 0;
   int lg_n_opt = 0;            // RT_HIP_SHADOW_GRID_N; 0 = 128, or 768 above kBvhAlwaysAbove spheres
   double lg_max_off = 0.0;
   bool lg_off_free = false;  // shadow queries skip the per-ray max_off check (light_grids)
@@ -1865,12 +1961,14 @@ struct rt_ctx {
   int cg_n_opt = 0;   // RT_HIP_CAM_GRID_N (tuning build); 0 = kCgNStatic / kCgNMoving
   long long cg_budget_opt = -1;  // RT_HIP_CAM_GRID_BUDGET (tuning build): bytes for a launch's grids; -1 = kCgBudgetBytes
   long long cg_maxp_opt = -1;    // RT_HIP_CAM_GRID_MAXP (tuning build): pairs per grid kept; -1 = the pair budget
-  int32_t *d_cg_count = nullptr;
-  int2 *d_cg_ent = nullptr;
-  CgDisk *d_cg_disks = nullptr;
-  int2 *d_cg_pairs = nullptr;
-  unsigned *d_cg_npairs = nullptr;
-  size_t cg_count_cap = 0, cg_ent_cap = 0, cg_disks_cap = 0, cg_pairs_cap = 0, cg_npairs_cap = 0;  // bytes
+  DevBuf<int32_t> cg_count;
+  DevBuf<int2> cg_ent;
+  DevBuf<CgDisk> cg_disks;
+  DevBuf<int2> cg_pairs;
+  DevBuf<unsigned> cg_npairs;
+  size_t cg_bytes() const {
+    return cg_count.bytes() + cg_ent.bytes() + cg_disks.bytes() + cg_pairs.bytes() + cg_npairs.bytes();
+  }
   int cg_n = 0, cg_ngrid = 0;
   std::vector<double> cg_pos;          // the grids' points (3 per grid)
   std::vector<double> cg_seen;         // the previous launch's camera positions
@@ -1878,55 +1976,27 @@ struct rt_ctx {
   unsigned long long cg_gen = ~0ull;   // scene_gen they were built for
   struct CgTables {                    // the cube map's patch tables of one N on the device
     int N = 0, NT = 0, NB = 0;
-    CubePatch *faces = nullptr, *blocks = nullptr, *tiles = nullptr;
-    double *cell = nullptr;
+    DevBuf<CubePatch> faces, blocks, tiles;
+    DevBuf<double> cell;
   };
   CgTables cg_tab[2];
   int cg_tab_next = 0;
-  std::vector<double> h_sx, h_sy, h_sz, h_sr;  // sphere centres and radii (grid builds)
-  // sphere grids (rt_lightgrid.h build_sphere_grids): the closest hit of
-  // reflection rays in the kFast kernels, built at upload for the reflective
-  // spheres
+  // sphere grids (Scene::sg_*)
   int sg_mode = -1;  // RT_HIP_SPHERE_GRID: -1 auto (scenes of up to kSgMaxSpheres spheres), 0 off, 1 on
   int sg_n_opt = 0;  // RT_HIP_SPHERE_GRID_N; 0 = kSgN
-  int32_t *d_sg_start = nullptr;
-  int2 *d_sg_ent = nullptr;
-  double *d_sg_rho2 = nullptr;
-  int sg_n = 0, sg_grids = 0;
-  long long sg_nstart = 0, sg_nent = 0;
-  bool sg_ok = false;
-  size_t sg_entries = 0;
   double sg_build_ms = 0.0;
-  // RT_HIP_SPHERE_GRID auto: the grids are built by the scene's first launch
-  // of more than one frame, or its second launch -- not by rt_upload_scene: a
-  // one-image render (the drop-in ray_serial) spends ~1.8 ms building 143
-  // grids (synth200) that save it ~0.05 ms of kernel time
-  std::vector<rt_sphere> sg_src;  // the uploaded spheres (centres, radii, reflectivities)
-  double sg_diam = 0.0;
-  bool sg_pending = false;
-  long long scene_launches = 0;  // render launches since the scene was uploaded
   double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds (rt_info)
   int nsph_up = 0;  // spheres of the scene being uploaded (the device grid builders)
-  // behind grid (rt_bvh.h build_ugrid): the backward half of the ordered
-  // walks' closest-hit lines (rt_device.h behind_cells), built at upload
+  // behind grid (Scene::ug_*), built at upload
   int ug_mode = -1;  // RT_HIP_BEHIND_GRID: -1 auto (scenes above kBvhAlwaysAbove spheres), 0 off, 1 on
   // RT_HIP_GRID_CLOSEST: 1 (default) = with the grid, closest hits walk it along the whole line instead of the
   // BVH (rt_device.h grid_closest_line; synth10k 3.03 -> 2.93 ms per frame, profiles/r3u); 0 = the ordered BVH
   // walk ahead of the origin + behind_cells behind it (3.15 ms: the grid walk behind the origin costs more than
   // the BVH boxes it replaces)
   int ug_closest = 1;
-  int32_t *d_ug_rid = nullptr, *d_ug_ids = nullptr, *d_ug_glob = nullptr;
-  UgRec *d_ug_rec = nullptr, *d_ug_q = nullptr;
   double ug_cells = 2.0;  // RT_HIP_GRID_CELLS: cells per listed sphere
-  UgArgs ug{};        // its device arguments (on = 0 until a launch allows it)
-  float ug_reg_margin = 0.0f, ug_extent = 0.0f;
-  bool ug_ok = false;
   bool ug_last = false;  // the most recent launch used it
-  size_t ug_entries = 0;
   double ug_build_ms = 0.0;
-  double c0[3] = {0, 0, 0};
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // bounds of spheres and lights
-  double rmax = 0;
   int bvh_min = 24, bvh_on = 1, bvh_groups = 2, bvh_leaf = 4;
   // RT_HIP_BVH_LEAF; 0 = 2, or 1 above kBvhAlwaysAbove spheres (rt_upload_scene)
   int bvh_leaf_opt = 0;
@@ -1934,26 +2004,21 @@ struct rt_ctx {
   // kBvhAlwaysAbove spheres (a linear cull sweep is O(n) per group)
   int bvh_always = -1;
   int n_cu = 256;
-  LightD *d_lights = nullptr;
-  int nsph = 0, nlight = 0;
-  double amb[3] = {0, 0, 0};
-  bool has_scene = false;
   // Counters: two halves of one allocation, alternating by launch; d_counters
   // is the half of the latest launch (what rt_render_stats reads).  A
   // render_kernel launch zeroes the other half for the next launch, so the
   // default path needs no separate memset (a fill kernel per frame).
-  unsigned long long *d_counters = nullptr;
-  unsigned long long *d_ctr_base = nullptr;
+  unsigned long long *d_counters = nullptr;  // into ctr_base
+  DevBuf<unsigned long long> ctr_base;
   bool ctr_clean[2] = {true, true};
   bool zero_pending = false;  // the launch being enqueued zeroes the other half
-  unsigned long long *h_counters = nullptr;  // pinned
+  PinnedBuf<unsigned long long> h_counters;
   // In-stream HIP events around every render launch (a ring), so a caller can
   // time a whole region of launches and read the per-launch durations after.
   static constexpr int kRing = 256;
   hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};
   long long launches = 0, hist_begin = 0;
-  uint8_t *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
+  DevBuf<uint8_t> tmp;  // rt_render to host memory: the image on the device
   int samples = 1;  // 4: the antialias mode (rt_set_antialias)
   int stack_mode = 4;  // RT_HIP_STACK: 4 merged reflection levels (default), 1 per-pixel global stack (one tile per wave)
   // RT_HIP_DEFER: kStackMerge defers rays of level >= kDeferLevel to render_deferred
@@ -1964,21 +2029,19 @@ struct rt_ctx {
   // per frame without it)
   int defer = -1;
   bool defer_walk = true;  // RT_HIP_DEFER_WALK: deferred rays of a scene whose closest hits always walk the BVH use render_deferred_walk
-  int merge_q = 64;           // kStackMerge: the launch's LDS queue entries per wave (launch_render4 picks it)
+  int merge_q = 64;           // kStackMerge: the launch's LDS queue entries per wave (launch_render picks it)
   int merge_q_max = 64;       // RT_HIP_MERGE_Q: longest queue tried (8, 16, 32 or 64)
   int defer_level = kDeferLevel;  // RT_HIP_DEFER_LEVEL (>= 1)
   int defer_div = RT_DEFER_CAP_DIV;  // RT_HIP_DEFER_DIV (tuning build): queue room = launch pixels / defer_div
-  QRay *dq_buf = nullptr;     // its queue (and its slots' stacks), grow-only
+  DevBuf<QRay> dq;            // its queue (and its slots' stacks), grow-only
   // kStackMerge: the merged waves' stack homes (merge_tiles, home_acquire),
   // twice as many as the render kernel can have resident, and their bitmap
-  StackEnt *d_homes = nullptr;
-  size_t homes_bytes = 0;
-  unsigned long long *d_home_bits = nullptr;
-  int home_words = 0;
+  // (one bit per home)
+  DevBuf<StackEnt> homes;
+  DevBuf<unsigned long long> home_bits;
   const void *occ_kernel = nullptr;  // the occupancy of the last kernel asked (blocks per CU at occ_lds)
   size_t occ_lds = 0;
   int occ_blocks = 0;
-  size_t dq_bytes = 0;
   // frames of the launch being enqueued (rt_render_frames_async; 1 otherwise) and their cameras
   int nframes = 1;
   const rt_camera *fcams = nullptr;
@@ -1986,10 +2049,9 @@ struct rt_ctx {
   // launch-order buffer of the blocks covering them
   const rt_tile *req_tiles = nullptr;
   int req_n = 0;
-  int *d_bperm = nullptr, *h_bperm = nullptr;  // h_bperm pinned
-  size_t bperm_cap = 0;
-  unsigned char *cstack_buf = nullptr;
-  size_t cstack_bytes = 0;
+  DevBuf<int> bperm;
+  PinnedBuf<int> h_bperm;
+  DevBuf<StackEnt> gstack;  // kStackGlobal: the per-pixel reflection stack, grow-only
   // RT_HIP_LDS_SCENE=1: stage scenes that fit (<= kLdsBudget) in LDS, 4-wave
   // workgroups.  Off by default: one-wave workgroups reading the scene through
   // L2 free each wave's slot as soon as its own tile is done (synth200:
@@ -1998,12 +2060,11 @@ struct rt_ctx {
   // Launch order of the tiles (rt_sched.h), rebuilt when the view or the
   // scene changes; RT_HIP_SCHED=0 dispatches in scanline order.
   int sched = 1;
-  std::vector<SchedSphere> h_refl;  // reflective spheres of the scene
   unsigned long long scene_gen = 0;
   SchedView perm_view{};
   unsigned long long perm_gen = ~0ull;
-  int *d_perm = nullptr, *h_perm = nullptr;  // h_perm pinned
-  size_t perm_cap = 0;
+  DevBuf<int> perm;
+  PinnedBuf<int> h_perm;
   long long perm_cls[kSchedClasses] = {};  // tiles per class of the cached order
   // kStackMerge: tiles of this class and above get a wave each (RT_HIP_SINGLE_CLASS
   // for every launch; kSchedClasses = none).  Default: every tile (class >= 0)
@@ -2060,98 +2121,57 @@ int fail(rt_ctx *c, hipError_t e, const char *what) {
   } while (0)
 
 void free_scene(rt_ctx *c) {
-  if (c->d_geo) (void)hipFree(c->d_geo);
-  if (c->d_rad) (void)hipFree(c->d_rad);
-  if (c->d_mat) (void)hipFree(c->d_mat);
-  if (c->d_lights) (void)hipFree(c->d_lights);
-  if (c->d_bvh) (void)hipFree(c->d_bvh);
-  if (c->d_prims) (void)hipFree(c->d_prims);
-  if (c->d_pf) (void)hipFree(c->d_pf);
-  c->d_pf = nullptr;
-  if (c->d_bvh2) (void)hipFree(c->d_bvh2);
-  c->d_bvh2 = nullptr;
-  if (c->d_bvh4) (void)hipFree(c->d_bvh4);
-  c->d_bvh4 = nullptr;
-  if (c->d_lg_start) (void)hipFree(c->d_lg_start);
-  if (c->d_lg_ids) (void)hipFree(c->d_lg_ids);
-  c->d_lg_start = c->d_lg_ids = nullptr;
+  c->scene = Scene{};
   c->cg_gen = ~0ull;
-  if (c->d_sg_start) (void)hipFree(c->d_sg_start);
-  if (c->d_sg_ent) (void)hipFree(c->d_sg_ent);
-  if (c->d_sg_rho2) (void)hipFree(c->d_sg_rho2);
-  c->d_sg_start = nullptr;
-  c->d_sg_ent = nullptr;
-  c->d_sg_rho2 = nullptr;
-  c->sg_ok = false;
-  c->sg_pending = false;
-  c->sg_grids = 0;
-  c->sg_entries = 0;
-  if (c->d_ug_rec) (void)hipFree(c->d_ug_rec);
-  if (c->d_ug_rid) (void)hipFree(c->d_ug_rid);
-  if (c->d_ug_ids) (void)hipFree(c->d_ug_ids);
-  if (c->d_ug_glob) (void)hipFree(c->d_ug_glob);
-  if (c->d_ug_q) (void)hipFree(c->d_ug_q);
-  c->d_ug_rid = c->d_ug_ids = c->d_ug_glob = nullptr;
-  c->d_ug_rec = c->d_ug_q = nullptr;
-  c->ug = UgArgs{};
-  c->ug_ok = false;
-  c->ug_entries = 0;
-  c->d_bvh = nullptr;
-  c->d_prims = nullptr;
-  c->bvh_nodes = 0;
-  c->d_geo = nullptr;
-  c->d_rad = nullptr;
-  c->d_mat = nullptr;
-  c->d_lights = nullptr;
-  c->has_scene = false;
 }
 
 // BVH arguments for one render: the scene extent includes the camera (the
 // origin of primary rays); margin = 1e-6 * (diameter + largest radius).
 BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
+  const Scene &sc = c->scene;
   BvhArgs b{};
-  b.nodes = c->d_bvh;
-  b.prims = c->d_prims;
-  b.pf = c->d_pf;
-  b.n2 = c->d_bvh2;
-  b.root_ref = c->bvh2_root;
-  b.nnodes = (c->bvh_on && c->cull) ? c->bvh_nodes : 0;
-  b.nn2 = c->bvh2_nodes;
-  b.nn4 = c->bvh4_nodes;
-  b.nprims = c->bvh_prims;
-  b.n4 = c->d_bvh4;
-  b.root4 = c->bvh4_root;
-  b.wide = (c->bvh_wide && c->d_bvh4 && c->bvh4_stack <= kOrderedStack) ? 1 : 0;
-  b.ordered = (c->bvh_ordered && b.nnodes > 0 && (b.wide || (c->d_bvh2 && c->bvh_depth <= kOrderedStack))) ? 1 : 0;
+  b.nodes = sc.bvh.get();
+  b.prims = sc.prims.get();
+  b.pf = sc.pf.get();
+  b.n2 = sc.bvh2.get();
+  b.root_ref = sc.bvh2_root;
+  b.nnodes = (c->bvh_on && c->cull) ? sc.bvh_nodes : 0;
+  b.nn2 = sc.bvh2_nodes;
+  b.nn4 = sc.bvh4_nodes;
+  b.nprims = sc.bvh_prims;
+  b.n4 = sc.bvh4.get();
+  b.root4 = sc.bvh4_root;
+  b.wide = (c->bvh_wide && b.n4 && sc.bvh4_stack <= kOrderedStack) ? 1 : 0;
+  b.ordered = (c->bvh_ordered && b.nnodes > 0 && (b.wide || (b.n2 && sc.bvh_depth <= kOrderedStack))) ? 1 : 0;
   if (!b.ordered) b.wide = 0;
-  b.odepth = std::max(1, b.wide ? c->bvh4_stack : c->bvh_depth);
+  b.odepth = std::max(1, b.wide ? sc.bvh4_stack : sc.bvh_depth);
   b.ostk = nullptr;  // set in the kernel (LDS), or found at ostk_off
   b.ostk_off = -1;
-  b.c0x = c->c0[0];
-  b.c0y = c->c0[1];
-  b.c0z = c->c0[2];
+  b.c0x = sc.c0[0];
+  b.c0y = sc.c0[1];
+  b.c0z = sc.c0[2];
   const double cp[3] = {cam.px, cam.py, cam.pz};
   double d2 = 0.0;
   for (int k = 0; k < 3; k++) {
-    const double l = std::min(c->lo[k], cp[k]), h = std::max(c->hi[k], cp[k]);
+    const double l = std::min(sc.lo[k], cp[k]), h = std::max(sc.hi[k], cp[k]);
     d2 += (h - l) * (h - l);
   }
   b.diam = std::sqrt(d2) + 0.01;  // + the 0.001 origin offsets of secondary rays
-  const double m = 1e-6 * (b.diam + c->rmax);
+  const double m = 1e-6 * (b.diam + sc.rmax);
   b.margin = std::isfinite(m) ? (float)(m * (1.0 + 1e-6)) : INFINITY;
   b.pmargin = 4.0f * b.margin;
   if (!std::isfinite(b.diam)) b.diam = INFINITY;
   b.min_cands = c->bvh_min;
-  b.always = c->bvh_always >= 0 ? c->bvh_always : (c->nsph > kBvhAlwaysAbove ? 1 : 0);
+  b.always = c->bvh_always >= 0 ? c->bvh_always : (sc.nsph > kBvhAlwaysAbove ? 1 : 0);
   b.max_groups = c->bvh_groups;
   // the behind grid, when its listing margin covers this view's prefilter
   // margin plus the DDA's error bound (rt_device.h behind_cells); the ordered
   // walks then skip boxes wholly behind the origin
   b.tf_min = -INFINITY;
   b.ug = UgArgs{};
-  if (c->ug_ok && b.nnodes > 0 && b.ordered && b.wide && std::isfinite(b.pmargin) &&
-      (double)b.pmargin + 1e-4 * (double)c->ug_extent <= (double)c->ug_reg_margin) {
-    b.ug = c->ug;
+  if (sc.ug_ok && b.nnodes > 0 && b.ordered && b.wide && std::isfinite(b.pmargin) &&
+      (double)b.pmargin + 1e-4 * (double)sc.ug_extent <= (double)sc.ug_reg_margin) {
+    b.ug = sc.ug;
     b.ug.on = 1;
     b.ug.closest = c->ug_closest;
     b.tf_min = 0.0f;
@@ -2165,14 +2185,14 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
 
 LgArgs lg_args(const rt_ctx *c) {
   LgArgs g{};
-  g.start = c->d_lg_start;
-  g.ids = c->d_lg_ids;
+  g.start = c->scene.lg_start.get();
+  g.ids = c->scene.lg_ids.get();
   g.N = c->lg_n;
-  g.on = (c->lg_on && c->cull && c->d_lg_start) ? 1 : 0;
+  g.on = (c->lg_on && c->cull && g.start) ? 1 : 0;
   g.max_off = c->lg_max_off;
   g.off_free = c->lg_off_free ? 1 : 0;
-  g.nstart = c->lg_nstart;
-  g.nids = c->lg_nids;
+  g.nstart = c->scene.lg_nstart;
+  g.nids = c->scene.lg_nids;
   return g;
 }
 
@@ -2183,7 +2203,6 @@ LgArgs lg_args(const rt_ctx *c) {
 // a grid per frame (a quarter of the cells to build)
 constexpr int kCgNStatic = 256, kCgNMoving = 128;
 
-void free_tables(rt_ctx::CgTables &t);
 int upload_tables(rt_ctx *c, int N, rt_ctx::CgTables &t);
 
 // The device patch tables of the cube map with N cells per face edge (two
@@ -2197,17 +2216,11 @@ int cg_tables(rt_ctx *c, int N, const rt_ctx::CgTables *&out) {
   rt_ctx::CgTables &t = c->cg_tab[c->cg_tab_next];
   c->cg_tab_next ^= 1;
   RT_TRY(c, hipStreamSynchronize(c->stream));
-  free_tables(t);
+  t = rt_ctx::CgTables{};
   const int rc = upload_tables(c, N, t);
   if (rc != RT_OK) return rc;
   out = &t;
   return RT_OK;
-}
-
-void free_tables(rt_ctx::CgTables &t) {
-  for (void *p : {(void *)t.faces, (void *)t.blocks, (void *)t.tiles, (void *)t.cell})
-    if (p) (void)hipFree(p);
-  t = rt_ctx::CgTables{};
 }
 
 // The cube map's patch tables for N cells per face edge, on the device.
@@ -2216,48 +2229,37 @@ int upload_tables(rt_ctx *c, int N, rt_ctx::CgTables &t) {
   std::vector<double> cell;
   int NT = 0, NB = 0;
   cube_tables(N, faces, blocks, tiles, cell, NT, NB);
-  RT_TRY(c, hipMalloc(&t.faces, faces.size() * sizeof(CubePatch)));
-  RT_TRY(c, hipMalloc(&t.blocks, blocks.size() * sizeof(CubePatch)));
-  RT_TRY(c, hipMalloc(&t.tiles, tiles.size() * sizeof(CubePatch)));
-  RT_TRY(c, hipMalloc(&t.cell, cell.size() * sizeof(double)));
-  RT_TRY(c, hipMemcpy(t.faces, faces.data(), faces.size() * sizeof(CubePatch), hipMemcpyHostToDevice));
-  RT_TRY(c, hipMemcpy(t.blocks, blocks.data(), blocks.size() * sizeof(CubePatch), hipMemcpyHostToDevice));
-  RT_TRY(c, hipMemcpy(t.tiles, tiles.data(), tiles.size() * sizeof(CubePatch), hipMemcpyHostToDevice));
-  RT_TRY(c, hipMemcpy(t.cell, cell.data(), cell.size() * sizeof(double), hipMemcpyHostToDevice));
+  RT_TRY(c, t.faces.upload(faces));
+  RT_TRY(c, t.blocks.upload(blocks));
+  RT_TRY(c, t.tiles.upload(tiles));
+  RT_TRY(c, t.cell.upload(cell));
   t.N = N;
   t.NT = NT;
   t.NB = NB;
   return RT_OK;
 }
 
-// grow-only device buffer
-template <class T>
-int grow(rt_ctx *c, T *&p, size_t &cap, size_t bytes) {
-  if (cap >= bytes) return RT_OK;
+// grow-only buffer (device or pinned)
+template <class B>
+int grow(rt_ctx *c, B &b, size_t bytes) {
+  if (b.bytes() >= bytes) return RT_OK;
   RT_TRY(c, hipStreamSynchronize(c->stream));  // launches in flight may read the old one
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  RT_TRY(c, hipMalloc(&p, bytes));
-  cap = bytes;
+  b.reset();
+  RT_TRY(c, b.alloc(bytes));
   return RT_OK;
 }
 
-// grow-only device buffer that may fail softly: false (error cleared, buffer
-// freed) when the memory is not there -- for optional structures
-template <class T>
-bool grow_soft(rt_ctx *c, T *&p, size_t &cap, size_t bytes) {
-  if (cap >= bytes) return true;
+// grow-only buffer that may fail softly: false (error cleared, buffer freed)
+// when the memory is not there -- for optional structures
+template <class B>
+bool grow_soft(rt_ctx *c, B &b, size_t bytes) {
+  if (b.bytes() >= bytes) return true;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  if (hipMalloc(&p, bytes) != hipSuccess) {
+  b.reset();
+  if (b.alloc(bytes) != hipSuccess) {
     (void)hipGetLastError();
-    p = nullptr;
     return false;
   }
-  cap = bytes;
   return true;
 }
 
@@ -2287,7 +2289,8 @@ struct CgPlan {
 // stream ahead of the render kernel.
 int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
   p = CgPlan{};
-  if (c->cg_mode == 0 || !c->cull || c->nsph == 0) return RT_OK;
+  const int nsph = c->scene.nsph;
+  if (c->cg_mode == 0 || !c->cull || nsph == 0) return RT_OK;
   std::vector<double> pos{cam.px, cam.py, cam.pz};
   bool same = true;
   for (int f = 1; f < nf; f++) same = same && std::memcmp(c->fcams[f].position, pos.data(), 3 * sizeof(double)) == 0;
@@ -2322,14 +2325,14 @@ int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
   // pairs per grid: every (disk, block) pair at most, within the pair budget
   // (a grid past it is marked overflowed on the device), and 4 work items per
   // pair of all grids countable in 32 bits (cg_bin_kernel)
-  const unsigned long long worst = 2ull * (unsigned long long)c->nsph * (unsigned long long)nblocks;
+  const unsigned long long worst = 2ull * (unsigned long long)nsph * (unsigned long long)nblocks;
   const unsigned long long cap32 = ((1ull << 32) - 1) / (4ull * (unsigned long long)ngrid);
   const unsigned long long budget = std::max<unsigned long long>(1, kCgPairBytes / sizeof(int2) / ngrid);
   int maxp = (int)std::min({worst, cap32, budget, (unsigned long long)INT32_MAX});
   if (c->cg_maxp_opt >= 0) maxp = (int)std::max<long long>(1, std::min<long long>(maxp, c->cg_maxp_opt));
   const size_t b_count = ngrid * cells * sizeof(int32_t), b_ent = ngrid * cells * kCgSlots * sizeof(int2),
                b_np = (size_t)ngrid * kCgCntStride * sizeof(unsigned),
-               b_disks = 2 * (size_t)c->nsph * ngrid * sizeof(CgDisk), b_pairs = (size_t)ngrid * maxp * sizeof(int2);
+               b_disks = 2 * (size_t)nsph * ngrid * sizeof(CgDisk), b_pairs = (size_t)ngrid * maxp * sizeof(int2);
   const size_t total = b_count + b_ent + b_np + b_disks + b_pairs;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
@@ -2337,12 +2340,11 @@ int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
     free_b = 0;
   }
   // what the grids hold now counts as available: growing frees it first
-  const size_t held = c->cg_count_cap + c->cg_ent_cap + c->cg_npairs_cap + c->cg_disks_cap + c->cg_pairs_cap;
+  const size_t held = c->cg_bytes();
   const size_t limit = c->cg_budget_opt >= 0 ? (size_t)c->cg_budget_opt : kCgBudgetBytes;
   if (total > limit || total > (free_b + held) / 2) return RT_OK;
-  if (!grow_soft(c, c->d_cg_count, c->cg_count_cap, b_count) || !grow_soft(c, c->d_cg_ent, c->cg_ent_cap, b_ent) ||
-      !grow_soft(c, c->d_cg_npairs, c->cg_npairs_cap, b_np) || !grow_soft(c, c->d_cg_disks, c->cg_disks_cap, b_disks) ||
-      !grow_soft(c, c->d_cg_pairs, c->cg_pairs_cap, b_pairs))
+  if (!grow_soft(c, c->cg_count, b_count) || !grow_soft(c, c->cg_ent, b_ent) || !grow_soft(c, c->cg_npairs, b_np) ||
+      !grow_soft(c, c->cg_disks, b_disks) || !grow_soft(c, c->cg_pairs, b_pairs))
     return RT_OK;  // no memory for the grid: this launch sweeps
   p.use = p.build = true;
   p.N = N;
@@ -2363,19 +2365,19 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
     const rt_ctx::CgTables *tab = p.tab;
     const int ngrid = p.ngrid;
     CgBuild b{};
-    b.geo = c->d_geo;
-    b.rad = c->d_rad;
-    b.faces = tab->faces;
-    b.blocks = tab->blocks;
-    b.tiles = tab->tiles;
-    b.cell_cbsb = tab->cell;
-    b.count = c->d_cg_count;
-    b.ent = c->d_cg_ent;
-    b.disks = c->d_cg_disks;
-    b.pairs = c->d_cg_pairs;
-    b.npairs = c->d_cg_npairs;
+    b.geo = c->scene.geo.get();
+    b.rad = c->scene.rad.get();
+    b.faces = tab->faces.get();
+    b.blocks = tab->blocks.get();
+    b.tiles = tab->tiles.get();
+    b.cell_cbsb = tab->cell.get();
+    b.count = c->cg_count.get();
+    b.ent = c->cg_ent.get();
+    b.disks = c->cg_disks.get();
+    b.pairs = c->cg_pairs.get();
+    b.npairs = c->cg_npairs.get();
     b.maxp = p.maxp;
-    b.n = c->nsph;
+    b.n = c->scene.nsph;
     b.N = p.N;
     b.NT = tab->NT;
     b.NB = tab->NB;
@@ -2387,14 +2389,14 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
       b.pz[g] = p.pos[3 * g + 2];
       double d2 = 0.0;  // the scene's extent with the point (the grown radius' margin)
       for (int k = 0; k < 3; k++) {
-        const double l = std::min(c->lo[k], p.pos[3 * g + k]), h = std::max(c->hi[k], p.pos[3 * g + k]);
+        const double l = std::min(c->scene.lo[k], p.pos[3 * g + k]), h = std::max(c->scene.hi[k], p.pos[3 * g + k]);
         d2 += (h - l) * (h - l);
       }
       b.diam[g] = std::sqrt(d2);
     }
-    RT_TRY(c, hipMemsetAsync(c->d_cg_count, 0, ngrid * cells * sizeof(int32_t), c->stream));
-    RT_TRY(c, hipMemsetAsync(c->d_cg_npairs, 0, ngrid * kCgCntStride * sizeof(unsigned), c->stream));
-    const int nthr = c->nsph * ngrid;
+    RT_TRY(c, hipMemsetAsync(b.count, 0, ngrid * cells * sizeof(int32_t), c->stream));
+    RT_TRY(c, hipMemsetAsync(b.npairs, 0, ngrid * kCgCntStride * sizeof(unsigned), c->stream));
+    const int nthr = b.n * ngrid;
     hipLaunchKernelGGL(cg_disk_kernel, dim3((unsigned)((nthr + 3) / 4)), dim3(256), 0, c->stream, b);
     hipLaunchKernelGGL(cg_bin_kernel, dim3((unsigned)std::min<long long>(8192, 8LL * nthr * p.nblocks)), dim3(64), 0,
                        c->stream, b);
@@ -2408,7 +2410,7 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
     c->cg_builds++;
     c->cg_build_ms += ms_since(t0);
   }
-  out = CgArgs{c->d_cg_count, c->d_cg_ent, p.N, 1, p.ngrid > 1 ? 1 : 0, p.ngrid};
+  out = CgArgs{c->cg_count.get(), c->cg_ent.get(), p.N, 1, p.ngrid > 1 ? 1 : 0, p.ngrid};
   return RT_OK;
 }
 
@@ -2422,20 +2424,13 @@ constexpr size_t kSgMaxEntries = size_t(256) << 20;  // 2 GiB of lists (built on
 
 // device scratch of one upload-time build, freed on every exit path
 struct DevScratch {
-  std::vector<void *> p;
+  std::vector<DevBuf<unsigned char>> bufs;
   template <class T>
   hipError_t alloc(T *&out, size_t bytes) {
-    out = nullptr;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-    if (e == hipSuccess) {
-      p.push_back(q);
-      out = static_cast<T *>(q);
-    }
+    bufs.emplace_back();
+    const hipError_t e = bufs.back().alloc(bytes);
+    out = reinterpret_cast<T *>(bufs.back().get());
     return e;
-  }
-  ~DevScratch() {
-    for (void *q : p) (void)hipFree(q);
   }
 };
 
@@ -2460,7 +2455,7 @@ int device_scan(rt_ctx *c, const int *x, long long n, int *y, long long &total) 
 // max_global global spheres or dropped pairs; light grids: never), the CSR
 // offsets of the ng x row lists (device, ng * row + 1 ints, held by `keep`)
 // and the entries (`out`: int2 (sphere, tlo) or, for light grids, int ids;
-// the caller owns it; nullptr when the lists would exceed max_entries).
+// empty when the lists would exceed max_entries).
 struct PgMode {
   int sides, globlist, max_global;
   size_t max_entries;
@@ -2469,20 +2464,17 @@ struct PgMode {
   // complex within +-0.3 %, profiles/r5x/ab_lg_order.log)
   int near = 0;
 };
+template <class E>  // the entries: int2 for sphere grids, int32_t for light grids (md.globlist)
 int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<unsigned char> &allglob, double diam,
                 int N, const PgMode &md, DevScratch &keep, int *&d_off, std::vector<unsigned char> &ok,
-                long long &total, void *&out) {
+                long long &total, DevBuf<E> &out) {
   const int n = c->nsph_up, ng = (int)pts.size();
   const long long cells = 6LL * N * N, row = cells + (md.globlist ? 1 : 0);
-  out = nullptr;
+  out.reset();
   total = 0;
   ok.assign((size_t)ng, 0);
   rt_ctx::CgTables tab;
   int rc = upload_tables(c, N, tab);
-  struct TabGuard {
-    rt_ctx::CgTables &t;
-    ~TabGuard() { free_tables(t); }
-  } tab_guard{tab};
   if (rc != RT_OK) return rc;
   const long long nblocks = 6LL * tab.NB * tab.NB;
   // pairs kept per grid (past it a sphere grid is refused, as one past the
@@ -2515,12 +2507,12 @@ int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<uns
   RT_TRY(c, hipMemcpy(d_ag, allglob.data(), (size_t)ng, hipMemcpyHostToDevice));
   RT_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)(ng * row), c->stream));
   SgBuild b{};
-  b.geo = c->d_geo;
-  b.rad = c->d_rad;
-  b.faces = tab.faces;
-  b.blocks = tab.blocks;
-  b.tiles = tab.tiles;
-  b.cell_cbsb = tab.cell;
+  b.geo = c->scene.geo.get();
+  b.rad = c->scene.rad.get();
+  b.faces = tab.faces.get();
+  b.blocks = tab.blocks.get();
+  b.tiles = tab.tiles.get();
+  b.cell_cbsb = tab.cell.get();
   b.disks = d_disks;
   b.pairs = d_pairs;
   b.npairs = d_np;
@@ -2582,10 +2574,11 @@ int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<uns
       if (!ok[(size_t)j]) return RT_OK;
   if ((rc = device_scan(c, d_cnt, (long long)ng * row, d_off, total)) != RT_OK) return rc;
   if ((size_t)total > md.max_entries || total > INT32_MAX) return RT_OK;
-  const size_t esz = md.globlist ? sizeof(int32_t) : sizeof(int2);
-  RT_TRY(c, hipMalloc(&out, esz * ((size_t)total + 1)));
-  b.ent = md.globlist ? nullptr : static_cast<int2 *>(out);
-  b.ids = md.globlist ? static_cast<int32_t *>(out) : nullptr;
+  RT_TRY(c, out.alloc(sizeof(E) * ((size_t)total + 1)));
+  if constexpr (std::is_same<E, int2>::value)
+    b.ent = out.get();
+  else
+    b.ids = out.get();
   b.nent = total;
   RT_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)(ng * row), c->stream));
   for (int g0 = 0; g0 < ng; g0 += batch)
@@ -2593,7 +2586,7 @@ int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<uns
   const long long nlists = (long long)ng * row;
   if (md.globlist)
     hipLaunchKernelGGL(ids_sort_kernel, dim3((unsigned)((nlists + 255) / 256)), dim3(256), 0, c->stream, d_off, nlists,
-                       b.ids, c->d_geo, d_pts, row, md.near);
+                       b.ids, b.geo, d_pts, row, md.near);
   else
     hipLaunchKernelGGL(sg_sort_kernel, dim3((unsigned)((nlists + 255) / 256)), dim3(256), 0, c->stream, d_off, nlists,
                        b.ent);
@@ -2609,16 +2602,19 @@ int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<uns
 // device (point_grids; the geometry is on the device already).  No grids (and
 // RT_OK) when disabled, too large, or refused.
 int sphere_grids(rt_ctx *c) {
-  const int n = (int)c->sg_src.size();
-  const double diam = c->sg_diam;
-  c->sg_pending = false;
+  Scene &scn = c->scene;
+  std::vector<rt_sphere> src;  // the scene's copy of the spheres ends with this build
+  src.swap(scn.sg_src);
+  const int n = (int)src.size();
+  const double diam = scn.sg_diam;
+  scn.sg_pending = false;
   if (c->sg_mode == 0 || (c->sg_mode < 0 && n > kSgMaxSpheres) || n == 0 || !std::isfinite(diam)) return RT_OK;
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<double> rho((size_t)n, -1.0);
   std::vector<int> gidx((size_t)n, -1);
   std::vector<GridPt> pts;
   for (int i = 0; i < n; i++) {
-    const rt_sphere &sp = c->sg_src[(size_t)i];
+    const rt_sphere &sp = src[(size_t)i];
     const double r = std::fabs(sp.radius);
     const double mag = std::fabs(sp.center[0]) + std::fabs(sp.center[1]) + std::fabs(sp.center[2]);
     if (sp.reflectivity > 0.0 && std::isfinite(r) && std::isfinite(mag))  // main.cpp:43
@@ -2636,24 +2632,27 @@ int sphere_grids(rt_ctx *c) {
   const size_t nstart = (size_t)n * (size_t)(cells + 1);
   if (nstart > (size_t)INT32_MAX || nstart * sizeof(int32_t) > ((size_t)1 << 30)) return RT_OK;
   const int ng = (int)pts.size();
-  c->sg_grids = 0;
-  c->sg_entries = 0;
+  scn.sg_grids = 0;
+  scn.sg_entries = 0;
   if (ng == 0 || (long long)ng * cells >= INT32_MAX) {  // (32-bit CSR offsets)
     c->sg_build_ms = ms_since(t0);
     return RT_OK;
   }
+  // built in buffers of this call, handed to the scene when complete: a
+  // build that fails on the way leaves nothing behind
   DevScratch keep;
   int *d_off = nullptr;
   std::vector<unsigned char> ok;
   long long total = 0;
-  void *ent = nullptr;
+  DevBuf<int2> ent;
+  DevBuf<int32_t> start;
+  DevBuf<double> d_rho2;
   int rc = point_grids(c, pts, std::vector<unsigned char>((size_t)ng, 0), diam, N,
                        PgMode{2, 0, kSgMaxGlobal, kSgMaxEntries}, keep, d_off, ok, total, ent);
-  c->d_sg_ent = static_cast<int2 *>(ent);  // owned by the context from here (free_scene)
   if (rc != RT_OK) return rc;
   int grids = 0;
   for (int j = 0; j < ng; j++) grids += ok[(size_t)j];
-  if (!ent || grids == 0) {  // as build_sphere_grids past max_entries: no grids
+  if (!ent.get() || grids == 0) {  // as build_sphere_grids past max_entries: no grids
     c->sg_build_ms = ms_since(t0);
     return RT_OK;
   }
@@ -2664,35 +2663,127 @@ int sphere_grids(rt_ctx *c) {
   RT_TRY(c, sc.alloc(d_ok, (size_t)ng));
   RT_TRY(c, hipMemcpy(d_gidx, gidx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
   RT_TRY(c, hipMemcpy(d_ok, ok.data(), (size_t)ng, hipMemcpyHostToDevice));
-  RT_TRY(c, hipMalloc(&c->d_sg_start, sizeof(int32_t) * nstart));
-  RT_TRY(c, hipMalloc(&c->d_sg_rho2, sizeof(double) * (size_t)n));
+  RT_TRY(c, start.alloc(sizeof(int32_t) * nstart));
   hipLaunchKernelGGL(sg_start_kernel, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, c->stream, d_gidx, d_ok,
-                     d_off, n, cells, c->d_sg_start);
+                     d_off, n, cells, start.get());
   RT_TRY(c, hipGetLastError());
   std::vector<double> rho2((size_t)n);
   for (int i = 0; i < n; i++) {
     const int j = gidx[(size_t)i];
     rho2[(size_t)i] = (j >= 0 && ok[(size_t)j]) ? rho[(size_t)i] * rho[(size_t)i] : -1.0;
   }
-  RT_TRY(c, hipMemcpy(c->d_sg_rho2, rho2.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  RT_TRY(c, d_rho2.upload(rho2));
   RT_TRY(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-  c->sg_n = N;
-  c->sg_nstart = (long long)nstart;
-  c->sg_nent = total;
-  c->sg_ok = true;
-  c->sg_grids = grids;
-  c->sg_entries = (size_t)total;
+  scn.sg_start = std::move(start);
+  scn.sg_ent = std::move(ent);
+  scn.sg_rho2 = std::move(d_rho2);
+  scn.sg_n = N;
+  scn.sg_nstart = (long long)nstart;
+  scn.sg_nent = total;
+  scn.sg_ok = true;
+  scn.sg_grids = grids;
+  scn.sg_entries = (size_t)total;
   c->sg_build_ms = ms_since(t0);
   return RT_OK;
+}
+
+// The host half of rt_upload_scene: what the scene's device arrays are copied
+// from, built from the caller's scene without touching the device.
+struct StagedScene {
+  std::vector<SphGeo> geo;
+  std::vector<double> rad;
+  std::vector<SphMat> mat;
+  std::vector<LightD> lights;
+  // bounds of spheres and lights, their centre, the largest radius, the diameter
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, c0[3] = {0, 0, 0};
+  double rmax = 0.0, diam = 0.0;
+  std::vector<double> sx, sy, sz;      // sphere centres
+  std::vector<double> bx, by, bz, br;  // ... relative to c0 (the BVH's frame), and the radii
+  std::vector<BvhNode> nodes;
+  std::vector<int32_t> prims;
+  std::vector<float4> pf;  // prefilter records in leaf order (centre - c0 in fp32, |radius| rounded up)
+  std::vector<BvhNode2> nodes2;
+  std::vector<BvhNode4> nodes4;
+  int32_t root2 = -1, root4 = -1;
+  int depth2 = 0, stack4 = 0;
+  bool ug_built = false;  // the behind grid, when asked for and within kUgMaxEntries
+  UgridHost ug;
+  std::vector<SchedSphere> refl;   // reflective spheres (rt_sched.h)
+  double bvh_ms = 0.0, ug_ms = 0.0;  // the host time of the two builds
+};
+
+void stage_scene(const rt_scene *s, int bvh_leaf, bool want_ug, double ug_cells, StagedScene &st) {
+  const int n = s->num_spheres, nl = s->num_lights;
+  st.geo.resize(n), st.rad.resize(n), st.mat.resize(n), st.lights.resize(nl);
+  for (int i = 0; i < n; i++) {
+    const rt_sphere &sp = s->spheres[i];
+    st.geo[i] = SphGeo{sp.center[0], sp.center[1], sp.center[2], sp.radius * sp.radius};
+    st.rad[i] = sp.radius < 0 ? -sp.radius : sp.radius;
+    st.mat[i] = SphMat{sp.color[0], sp.color[1], sp.color[2], sp.reflectivity, sp.shininess, 0.0};
+    if (sp.reflectivity > 0.0)  // main.cpp:43
+      st.refl.push_back(SchedSphere{sp.center[0], sp.center[1], sp.center[2], sp.radius});
+  }
+  for (int i = 0; i < nl; i++) {
+    const rt_light &L = s->lights[i];
+    st.lights[i] = LightD{L.position[0], L.position[1], L.position[2], L.color[0], L.color[1], L.color[2]};
+  }
+  auto extend = [&](const double *p, double r) {
+    for (int k = 0; k < 3; k++) {
+      st.lo[k] = std::min(st.lo[k], p[k] - r);
+      st.hi[k] = std::max(st.hi[k], p[k] + r);
+    }
+  };
+  for (int i = 0; i < n; i++) {
+    const double r = std::fabs(s->spheres[i].radius);
+    extend(s->spheres[i].center, r);
+    if (r > st.rmax || r != r) st.rmax = r != r ? INFINITY : r;
+  }
+  for (int i = 0; i < nl; i++) extend(s->lights[i].position, 0.0);
+  double d2 = 0.0;
+  for (int k = 0; k < 3; k++) {
+    if (n + nl > 0) st.c0[k] = std::isfinite(st.lo[k] + st.hi[k]) ? 0.5 * (st.lo[k] + st.hi[k]) : 0.0;
+    d2 += (st.hi[k] - st.lo[k]) * (st.hi[k] - st.lo[k]);
+  }
+  st.diam = n + nl > 0 ? std::sqrt(d2) : 0.0;
+  st.sx.resize(n), st.sy.resize(n), st.sz.resize(n);
+  st.bx.resize(n), st.by.resize(n), st.bz.resize(n), st.br.resize(n);
+  for (int i = 0; i < n; i++) {
+    st.sx[i] = s->spheres[i].center[0];
+    st.sy[i] = s->spheres[i].center[1];
+    st.sz[i] = s->spheres[i].center[2];
+    st.bx[i] = st.sx[i] - st.c0[0];
+    st.by[i] = st.sy[i] - st.c0[1];
+    st.bz[i] = st.sz[i] - st.c0[2];
+    st.br[i] = s->spheres[i].radius;
+  }
+  const auto t_bvh = std::chrono::steady_clock::now();
+  build_bvh(st.bx.data(), st.by.data(), st.bz.data(), st.br.data(), n, bvh_leaf, st.nodes, st.prims);
+  st.pf.resize(st.prims.size());
+  for (size_t k = 0; k < st.prims.size(); k++) {
+    const int id = st.prims[k];
+    float rr = (float)std::fabs(st.br[id]);
+    if ((double)rr < std::fabs(st.br[id])) rr = std::nextafter(rr, INFINITY);
+    st.pf[k] = make_float4((float)st.bx[id], (float)st.by[id], (float)st.bz[id], rr);
+  }
+  st.root2 = build_bvh2(st.nodes, st.nodes2, st.depth2);
+  st.root4 = build_bvh4(st.nodes, st.nodes4, st.stack4);
+  st.bvh_ms = ms_since(t_bvh);
+  if (want_ug) {
+    const auto t_ug = std::chrono::steady_clock::now();
+    st.ug_built = build_ugrid(st.bx.data(), st.by.data(), st.bz.data(), st.br.data(), n, kUgMaxEntries, st.ug, ug_cells);
+    st.ug_ms = ms_since(t_ug);
+  }
 }
 
 // The per-light direction grids for shadow rays (rt_lightgrid.h
 // build_light_grid's lists and layout), built on the device (point_grids,
 // one side, global lists); the host builder when the device lists would not
 // fit 32-bit offsets.
-int light_grids(rt_ctx *c, const rt_scene *s, double diam) {
+int light_grids(rt_ctx *c, const rt_scene *s, const StagedScene &st) {
   const auto t0 = std::chrono::steady_clock::now();
   const int n = s->num_spheres, nl = s->num_lights, N = c->lg_n;
+  const double diam = st.diam;
+  Scene &scn = c->scene;
   const long long cells = 6LL * N * N;
   c->lg_max_off = std::isfinite(diam) ? 1e-7 * diam : 0.0;
   {
@@ -2701,7 +2792,7 @@ int light_grids(rt_ctx *c, const rt_scene *s, double diam) {
     // the shadow lines' computed distance from their light stays below
     // 2^-41 (1.01 B + 0.01) (shadow_cells), so the per-ray check can go
     double B = 0.0;
-    for (int k = 0; k < 3; k++) B = std::max(B, std::max(std::fabs(c->lo[k]), std::fabs(c->hi[k])));
+    for (int k = 0; k < 3; k++) B = std::max(B, std::max(std::fabs(st.lo[k]), std::fabs(st.hi[k])));
     c->lg_off_free = std::isfinite(B) && c->lg_max_off > 0.0 && 0x1p-41 * (1.01 * B + 0.01) <= c->lg_max_off;
   }
   const double dm = std::isfinite(diam) ? diam : 0.0;
@@ -2712,28 +2803,24 @@ int light_grids(rt_ctx *c, const rt_scene *s, double diam) {
     pts[(size_t)l] = GridPt{L.position[0], L.position[1], L.position[2], 0.0};
     allglob[(size_t)l] = !(std::isfinite(L.position[0]) && std::isfinite(L.position[1]) && std::isfinite(L.position[2]));
   }
-  int32_t *ids = nullptr;
   long long total = 0;
   bool dev = nl > 0 && (long long)nl * (cells + 2) < INT32_MAX;
   if (dev) {
     DevScratch keep;
     int *d_off = nullptr;
     std::vector<unsigned char> ok;
-    void *out = nullptr;
     int rc = point_grids(c, pts, allglob, dm, N, PgMode{1, 1, INT32_MAX, (size_t)INT32_MAX, 1}, keep, d_off,
-                         ok, total, out);
-    ids = static_cast<int32_t *>(out);
-    c->d_lg_ids = ids;  // owned by the context from here (free_scene)
+                         ok, total, scn.lg_ids);
     if (rc != RT_OK) return rc;
-    if (ids) {
+    if (scn.lg_ids.get()) {
       const long long nstart = (long long)nl * (cells + 2);
-      RT_TRY(c, hipMalloc(&c->d_lg_start, sizeof(int32_t) * (size_t)(nstart + 1)));
+      RT_TRY(c, scn.lg_start.alloc(sizeof(int32_t) * (size_t)(nstart + 1)));
       hipLaunchKernelGGL(lg_start_kernel, dim3((unsigned)((nstart + 255) / 256)), dim3(256), 0, c->stream, d_off, nl,
-                         cells, c->d_lg_start);
+                         cells, scn.lg_start.get());
       RT_TRY(c, hipGetLastError());
       RT_TRY(c, hipStreamSynchronize(c->stream));  // d_off is freed on return
-      c->lg_nstart = nstart;
-      c->lg_nids = total;
+      scn.lg_nstart = nstart;
+      scn.lg_nids = total;
     } else {
       dev = false;
     }
@@ -2746,18 +2833,12 @@ int light_grids(rt_ctx *c, const rt_scene *s, double diam) {
       lz[(size_t)l] = s->lights[l].position[2];
     }
     std::vector<int32_t> lg_start, lg_ids;
-    build_light_grid(c->h_sx.data(), c->h_sy.data(), c->h_sz.data(), c->h_sr.data(), n, lx.data(), ly.data(),
-                     lz.data(), nl, diam, N, lg_start, lg_ids);
-    c->lg_nstart = (long long)lg_start.size();
-    c->lg_nids = (long long)lg_ids.size();
-    if (c->d_lg_ids) (void)hipFree(c->d_lg_ids);
-    c->d_lg_ids = nullptr;
-    RT_TRY(c, hipMalloc(&c->d_lg_start, sizeof(int32_t) * (lg_start.size() + 1)));
-    RT_TRY(c, hipMalloc(&c->d_lg_ids, sizeof(int32_t) * (lg_ids.size() + 1)));
-    if (!lg_start.empty())
-      RT_TRY(c, hipMemcpy(c->d_lg_start, lg_start.data(), sizeof(int32_t) * lg_start.size(), hipMemcpyHostToDevice));
-    if (!lg_ids.empty())
-      RT_TRY(c, hipMemcpy(c->d_lg_ids, lg_ids.data(), sizeof(int32_t) * lg_ids.size(), hipMemcpyHostToDevice));
+    build_light_grid(st.sx.data(), st.sy.data(), st.sz.data(), st.br.data(), n, lx.data(), ly.data(), lz.data(), nl,
+                     diam, N, lg_start, lg_ids);
+    scn.lg_nstart = (long long)lg_start.size();
+    scn.lg_nids = (long long)lg_ids.size();
+    RT_TRY(c, scn.lg_start.upload(lg_start, 1));
+    RT_TRY(c, scn.lg_ids.upload(lg_ids, 1));
   }
   c->lg_build_ms = ms_since(t0);
   return RT_OK;
@@ -2779,33 +2860,28 @@ int tile_perm(rt_ctx *c, const Cam &cam, int W, int H, const Rows &rows, const O
   v.rx = cam.rx, v.ry = cam.ry, v.rz = cam.rz, v.ux = cam.ux, v.uy = cam.uy, v.uz = cam.uz, v.scale = cam.scale;
   v.W = W, v.H = H, v.band = rows.band, v.first = rows.first, v.stride = rows.stride, v.count = rows.count;
   v.x0 = od.x0, v.xw = od.xw, v.tw = tw, v.th = th;
-  if (c->perm_gen == c->scene_gen && std::memcmp(&v, &c->perm_view, sizeof v) == 0 && c->d_perm) {
-    out = c->d_perm;
+  if (c->perm_gen == c->scene_gen && std::memcmp(&v, &c->perm_view, sizeof v) == 0 && c->perm.get()) {
+    out = c->perm.get();
     return RT_OK;
   }
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<int> perm;
   long long cls[kSchedClasses] = {};
-  tile_order(v, c->h_refl, perm, cls);
+  tile_order(v, c->scene.refl, perm, cls);
   if ((long long)perm.size() != ntiles) return RT_ERR_INVALID_ARG;
   const size_t bytes = perm.size() * sizeof(int);
   RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous order may still be in flight from h_perm
-  if (c->perm_cap < bytes) {
-    if (c->d_perm) (void)hipFree(c->d_perm);
-    if (c->h_perm) (void)hipHostFree(c->h_perm);
-    c->d_perm = c->h_perm = nullptr;
-    c->perm_cap = 0;
+  if (c->perm.bytes() < bytes || c->h_perm.bytes() < bytes) {  // grow-only, the pair together
     c->perm_gen = ~0ull;
-    RT_TRY(c, hipMalloc(&c->d_perm, bytes));
-    RT_TRY(c, hipHostMalloc(&c->h_perm, bytes, hipHostMallocDefault));
-    c->perm_cap = bytes;
+    RT_TRY(c, c->perm.alloc(bytes));
+    RT_TRY(c, c->h_perm.alloc(bytes));
   }
-  std::memcpy(c->h_perm, perm.data(), bytes);
-  RT_TRY(c, hipMemcpyAsync(c->d_perm, c->h_perm, bytes, hipMemcpyHostToDevice, c->stream));
+  std::memcpy(c->h_perm.get(), perm.data(), bytes);
+  RT_TRY(c, hipMemcpyAsync(c->perm.get(), c->h_perm.get(), bytes, hipMemcpyHostToDevice, c->stream));
   c->perm_view = v;
   c->perm_gen = c->scene_gen;
   for (int k = 0; k < kSchedClasses; k++) c->perm_cls[k] = cls[k];
-  out = c->d_perm;
+  out = c->perm.get();
   c->perm_builds++;
   c->perm_build_ms += ms_since(t0);
   return RT_OK;
@@ -2816,86 +2892,114 @@ int tile_perm(rt_ctx *c, const Cam &cam, int W, int H, const Rows &rows, const O
 // kernel time.  enqueue() has recorded it already for launches with no kernel.
 hipError_t mark_start(rt_ctx *c) { return hipEventRecord(c->ev0[(int)(c->launches % rt_ctx::kRing)], c->stream); }
 
-template <bool kLds, bool kCull, int kSamples, int kStack>
-int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
+// Which render kernel a launch runs: the scene staged in LDS or read through
+// L2, the cull sweeps, 1 or 4 samples, kStackGlobal or kStackMerge; fast /
+// wide (kStackMerge only) are launch_tiles' to set.
+struct KernelSel {
+  bool lds, cull;
+  int samples, stack;
+  bool fast = false, wide = false;
+};
+
+// The two tables of kernel instantiations: every render and deferred kernel
+// of the build is named here and nowhere else.
+const void *render_kernel_fn(const KernelSel &s) {
+#define RT_RK(...) reinterpret_cast<const void *>(&render_kernel<__VA_ARGS__>)
+  if (s.stack == kStackMerge) {  // the scene through L2, one sample
+    if (s.cull)
+      return s.wide   ? RT_RK(false, true, 1, kStackMerge, true, true)
+             : s.fast ? RT_RK(false, true, 1, kStackMerge, true)
+                      : RT_RK(false, true, 1, kStackMerge);
+    return s.wide   ? RT_RK(false, false, 1, kStackMerge, true, true)
+           : s.fast ? RT_RK(false, false, 1, kStackMerge, true)
+                    : RT_RK(false, false, 1, kStackMerge);
+  }
+  static const void *const kGlobal[2][2][2] = {  // [lds][cull][samples == 4]
+      {{RT_RK(false, false, 1, kStackGlobal), RT_RK(false, false, 4, kStackGlobal)},
+       {RT_RK(false, true, 1, kStackGlobal), RT_RK(false, true, 4, kStackGlobal)}},
+      {{RT_RK(true, false, 1, kStackGlobal), RT_RK(true, false, 4, kStackGlobal)},
+       {RT_RK(true, true, 1, kStackGlobal), RT_RK(true, true, 4, kStackGlobal)}}};
+  return kGlobal[s.lds][s.cull][s.samples == 4];
+#undef RT_RK
+}
+
+// walk: render_deferred_walk; else render_deferred, with the light loop
+// spread over the lanes (wide) or the fast paths only (s.fast)
+const void *deferred_kernel_fn(const KernelSel &s, bool walk, bool wide) {
+#define RT_RD(...) reinterpret_cast<const void *>(&render_deferred<__VA_ARGS__>)
+  if (walk) return reinterpret_cast<const void *>(&render_deferred_walk);
+  if (s.cull) return wide ? RT_RD(true, true, true) : s.fast ? RT_RD(true, true) : RT_RD(true);
+  return wide ? RT_RD(false, true, true) : s.fast ? RT_RD(false, true) : RT_RD(false);
+#undef RT_RD
+}
+
+int launch_tiles(rt_ctx *c, KernelSel sel, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
                  const OutDesc &od) {
+  Scene &scn = c->scene;
   BvhArgs bv = bvh_args(c, cam);
   const LgArgs lg = lg_args(c);
-  constexpr int kWg = wg_waves<kLds>(), kWx = kWg == 4 ? 2 : 1, kWy = kWg / kWx;
+  const bool merge = sel.stack == kStackMerge;
+  const int kWg = sel.lds ? wg_waves<true>() : wg_waves<false>(), kWx = kWg == 4 ? 2 : 1, kWy = kWg / kWx;
   // the ordered walk's stacks follow the scene in LDS (render_kernel)
   if (bv.ordered)
-    bv.ostk_off = (int)((lds_layout(kLds, c->nsph, c->nlight, bv.nnodes).end + 31) & ~(size_t)31);
+    bv.ostk_off = (int)((lds_layout(sel.lds, scn.nsph, scn.nlight, bv.nnodes).end + 31) & ~(size_t)31);
   const int ntx = (od.xw + 8 * kWx - 1) / (8 * kWx), nty = (rows.count + 8 * kWy - 1) / (8 * kWy);
   const long long ntiles = (long long)ntx * nty;
   // frames of this launch (rt_render_frames_async)
   const int nf = c->nframes;
   if (nf < 1 || nf > RT_MAX_FRAMES) return RT_ERR_INVALID_ARG;
   // kStackMerge: one wave per kMergeTiles consecutive tile slots
-  long long nslots = kStack == kStackMerge ? (ntiles + kMergeTiles - 1) / kMergeTiles : ntiles;
+  long long nslots = merge ? (ntiles + kMergeTiles - 1) / kMergeTiles : ntiles;
   if (ntiles * nf > (1LL << 30)) return RT_ERR_INVALID_ARG;
   // rt_render_tiles: the launch visits the blocks (launch tiles) that overlap
   // a requested tile, in scanline order of the blocks
   const int *batch_perm = nullptr;
-  if constexpr (kStack == kStackGlobal) {
-    if (c->req_tiles) {
-      const int bw = 8 * kWx, bh = 8 * kWy;
-      std::vector<unsigned char> mark((size_t)ntiles, 0);
-      for (int i = 0; i < c->req_n; i++) {
-        const rt_tile &t = c->req_tiles[i];
-        // in 64 bits: a caller's x + width near INT_MAX must still clip to the image
-        const int x1 = (int)std::min<long long>(W, (long long)t.x + t.width);
-        const int j1 = (int)std::min<long long>(H, (long long)t.y + t.height);
-        if (t.x >= x1 || t.y >= j1) continue;
-        // framebuffer rows j (0 = bottom) are PPM rows H-1-j
-        const int y0 = H - j1, y1 = H - 1 - t.y;
-        for (int by = y0 / bh; by <= y1 / bh; by++)
-          for (int bx = t.x / bw; bx <= (x1 - 1) / bw; bx++) mark[(size_t)by * ntx + bx] = 1;
-      }
-      std::vector<int> list;
-      for (long long b = 0; b < ntiles; b++)
-        if (mark[(size_t)b]) list.push_back((int)b);
-      nslots = (long long)list.size();
-      if (nslots == 0) return RT_OK;
-      const size_t bytes = list.size() * sizeof(int);
-      RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous list may still be in flight from h_bperm
-      if (c->bperm_cap < bytes) {
-        if (c->d_bperm) (void)hipFree(c->d_bperm);
-        if (c->h_bperm) (void)hipHostFree(c->h_bperm);
-        c->d_bperm = c->h_bperm = nullptr;
-        c->bperm_cap = 0;
-        RT_TRY(c, hipMalloc(&c->d_bperm, bytes));
-        RT_TRY(c, hipHostMalloc(&c->h_bperm, bytes, hipHostMallocDefault));
-        c->bperm_cap = bytes;
-      }
-      std::memcpy(c->h_bperm, list.data(), bytes);
-      RT_TRY(c, hipMemcpyAsync(c->d_bperm, c->h_bperm, bytes, hipMemcpyHostToDevice, c->stream));
-      batch_perm = c->d_bperm;
+  if (!merge && c->req_tiles) {
+    const int bw = 8 * kWx, bh = 8 * kWy;
+    std::vector<unsigned char> mark((size_t)ntiles, 0);
+    for (int i = 0; i < c->req_n; i++) {
+      const rt_tile &t = c->req_tiles[i];
+      // in 64 bits: a caller's x + width near INT_MAX must still clip to the image
+      const int x1 = (int)std::min<long long>(W, (long long)t.x + t.width);
+      const int j1 = (int)std::min<long long>(H, (long long)t.y + t.height);
+      if (t.x >= x1 || t.y >= j1) continue;
+      // framebuffer rows j (0 = bottom) are PPM rows H-1-j
+      const int y0 = H - j1, y1 = H - 1 - t.y;
+      for (int by = y0 / bh; by <= y1 / bh; by++)
+        for (int bx = t.x / bw; bx <= (x1 - 1) / bw; bx++) mark[(size_t)by * ntx + bx] = 1;
     }
+    std::vector<int> list;
+    for (long long b = 0; b < ntiles; b++)
+      if (mark[(size_t)b]) list.push_back((int)b);
+    nslots = (long long)list.size();
+    if (nslots == 0) return RT_OK;
+    const size_t bytes = list.size() * sizeof(int);
+    RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous list may still be in flight from h_bperm
+    if (c->bperm.bytes() < bytes || c->h_bperm.bytes() < bytes) {  // grow-only, the pair together
+      RT_TRY(c, c->bperm.alloc(bytes));
+      RT_TRY(c, c->h_bperm.alloc(bytes));
+    }
+    std::memcpy(c->h_bperm.get(), list.data(), bytes);
+    RT_TRY(c, hipMemcpyAsync(c->bperm.get(), c->h_bperm.get(), bytes, hipMemcpyHostToDevice, c->stream));
+    batch_perm = c->bperm.get();
   }
-  D3 amb{c->amb[0], c->amb[1], c->amb[2]};
+  D3 amb{scn.amb[0], scn.amb[1], scn.amb[2]};
   lds = (lds + 31) & ~(size_t)31;
   // the kernel places the ordered walk's stacks from these same arguments
   if (bv.ordered)
     lds += (size_t)kWg * bv.odepth * 64 * sizeof(int2);
-  if (!kLds && kStack == kStackGlobal) lds += (size_t)kWg * 64 * sizeof(D3);  // parked colours (trace_wave)
-  if (kStack == kStackMerge)  // the wave's ray queue and finished pixels (merge_tiles)
+  if (!sel.lds && !merge) lds += (size_t)kWg * 64 * sizeof(D3);  // parked colours (trace_wave)
+  if (merge)  // the wave's ray queue and finished pixels (merge_tiles)
     lds += (size_t)c->merge_q * sizeof(QRay) + kPixbufBytes;
   StackEnt *gstack = nullptr;
-  if (depth > 1 && kStack == kStackGlobal) {
+  if (depth > 1 && !merge) {
     // the kernel indexes the stack with 32 bits: entry + level * npx < 2^32
     if ((unsigned long long)(depth - 1) * rows.count * od.xw * nf >= (1ull << 32)) return RT_ERR_INVALID_ARG;
     // grow-only: sized for this launch's frames; a later launch of as many
     // frames or fewer (a last partial batch) reuses it
-    const size_t need = (size_t)(depth - 1) * rows.count * od.xw * nf * sizeof(StackEnt);
-    if (c->cstack_bytes < need) {
-      RT_TRY(c, hipStreamSynchronize(c->stream));
-      if (c->cstack_buf) (void)hipFree(c->cstack_buf);
-      c->cstack_buf = nullptr;
-      c->cstack_bytes = 0;
-      RT_TRY(c, hipMalloc(&c->cstack_buf, need));
-      c->cstack_bytes = need;
-    }
-    gstack = reinterpret_cast<StackEnt *>(c->cstack_buf);
+    const int rc = grow(c, c->gstack, (size_t)(depth - 1) * rows.count * od.xw * nf * sizeof(StackEnt));
+    if (rc != RT_OK) return rc;
+    gstack = c->gstack.get();
   }
   const int *perm = nullptr;
   int nsingle = 0;
@@ -2909,7 +3013,7 @@ int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth,
   } else if (c->sched && ntiles >= kSchedMinTiles) {
     int rc = tile_perm(c, cam, W, H, rows, od, 8 * kWx, 8 * kWy, ntiles, perm);
     if (rc != RT_OK) return rc;
-    if (kStack == kStackMerge) {  // the heaviest classes lead the order: one wave per tile for them
+    if (merge) {  // the heaviest classes lead the order: one wave per tile for them
       // one-frame launches: the tiles under reflective spheres (class >= 1) a
       // wave each, the rest four per wave, the last ones (tail) single again
       // (synth200 0.314 -> 0.298 ms, complex 0.293 -> 0.286 against every tile
@@ -2928,12 +3032,12 @@ int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth,
   const bool xcd_frames = nf > 1 && (c->xcd_frames > 0 || (c->xcd_frames < 0 && bv.ug.on));
   const dim3 grid((unsigned)((xcd_frames ? (nslots + 7) / 8 * 8 : nslots) * nf));
   RenderArgs ra{};
-  ra.geo = c->d_geo;
-  ra.radius = c->d_rad;
-  ra.mat = c->d_mat;
-  ra.lights = c->d_lights;
-  ra.n = c->nsph;
-  ra.nl = c->nlight;
+  ra.geo = scn.geo.get();
+  ra.radius = scn.rad.get();
+  ra.mat = scn.mat.get();
+  ra.lights = scn.lights.get();
+  ra.n = scn.nsph;
+  ra.nl = scn.nlight;
   ra.amb = amb;
   ra.cam[0] = cam;
   for (int f = 1; f < nf; f++) ra.cam[f] = to_cam(c->fcams[f]);
@@ -2954,7 +3058,7 @@ int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth,
   ra.perm = perm;
   // zero the other counter half for the next launch (enqueue's alternation)
   const int next = (int)((c->launches + 1) & 1);
-  ra.zero_next = c->d_ctr_base + (size_t)next * kShards * kShardStride;
+  ra.zero_next = c->ctr_base.get() + (size_t)next * kShards * kShardStride;
   c->zero_pending = true;
   ra.dq = nullptr;
   ra.dq_cap = 0;
@@ -2962,13 +3066,13 @@ int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth,
   ra.nsingle = nsingle;
   ra.merge_end = (int)(ntiles - tail);
   // merge_tiles' pixel bytes: after the scene and the walk stacks, where render_kernel's park/queue region starts
-  ra.pix_off = (int)(((lds_layout(kLds, c->nsph, c->nlight, bv.nnodes).end + 31) & ~(size_t)31) +
+  ra.pix_off = (int)(((lds_layout(sel.lds, scn.nsph, scn.nlight, bv.nnodes).end + 31) & ~(size_t)31) +
                      (bv.ordered ? (size_t)kWg * bv.odepth * 64 * sizeof(int2) : 0));
   // row k of frame f starts at ptr + f fstride + 3 (k W + x): dword aligned for every k, f and x = 8i
   ra.rows_dword = ((reinterpret_cast<uintptr_t>(od.ptr) | (uintptr_t)(3 * (size_t)W) | (uintptr_t)od.fstride) & 3) == 0;
   ra.defer_level = c->defer_level;
   ra.xcd_frames = xcd_frames ? 1 : 0;
-  if (kStack == kStackMerge && (c->defer > 0 || (c->defer < 0 && nf > 1)) && depth > c->defer_level) {
+  if (merge && (c->defer > 0 || (c->defer < 0 && nf > 1)) && depth > c->defer_level) {
     // room for 1/8 of the launch's pixels (deferred rays are ~2 % on synth200); a ray
     // that finds its shard segment full simply continues in its merge_tiles lane.
     // Each queue slot has its chain's stack after the queue: [depth-1][kShards * cap]
@@ -2978,154 +3082,113 @@ int launch_tiles(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth,
     // the queue is a speed-up: past the 32-bit slot-stack index, or when the
     // memory is not there (grow_soft), the launch runs without deferral
     if (cap < (size_t)1 << 30 && (unsigned long long)cap * kShards * (unsigned)(depth - 1) < (1ull << 32) &&
-        grow_soft(c, c->dq_buf, c->dq_bytes, need)) {
-      ra.dq = c->dq_buf;
+        grow_soft(c, c->dq, need)) {
+      ra.dq = c->dq.get();
       ra.dq_cap = (int)cap;
-      ra.dstack = reinterpret_cast<StackEnt *>(c->dq_buf + cap * kShards);
+      ra.dstack = reinterpret_cast<StackEnt *>(c->dq.get() + cap * kShards);
     }
   }
-  if constexpr (kStack == kStackMerge && !kLds && kSamples == 1) {
-    // the default configuration (ordered 4-wide BVH walk, light grids) has kernels
-    // compiled with only those paths (kFast): no registers held for the others
-    const bool fast = bv.ordered && bv.wide && lg.on;
-    // the light loop of sparse waves spread over the lanes (shade_hit kWide, the default)
-    const bool wide = fast && (c->wide_mode >= 2 || (nf == 1 && c->wide_mode == 1));
-    if (depth > 1) {  // the stack homes: 2 x the render kernel's resident waves
-      const void *kf = wide   ? reinterpret_cast<const void *>(&render_kernel<kLds, kCull, kSamples, kStack, true, true>)
-                       : fast ? reinterpret_cast<const void *>(&render_kernel<kLds, kCull, kSamples, kStack, true>)
-                              : reinterpret_cast<const void *>(&render_kernel<kLds, kCull, kSamples, kStack>);
-      if (kf != c->occ_kernel || lds != c->occ_lds) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * kWg, lds) != hipSuccess || nb < 1) {
-          (void)hipGetLastError();
-          nb = 32;  // the most waves a CU holds
-        }
-        c->occ_kernel = kf;
-        c->occ_lds = lds;
-        c->occ_blocks = nb;
-      }
-      const int words = (int)(((long long)2 * c->occ_blocks * kWg * c->n_cu + 63) / 64);
-      const size_t hb = (size_t)words * 64 * (size_t)(depth - 1) * kHomePx * sizeof(StackEnt);
-      if (c->homes_bytes < hb || c->home_words < words) {
-        RT_TRY(c, hipStreamSynchronize(c->stream));  // launches in flight hold homes
-        if (c->d_homes) (void)hipFree(c->d_homes);
-        if (c->d_home_bits) (void)hipFree(c->d_home_bits);
-        c->d_homes = nullptr;
-        c->d_home_bits = nullptr;
-        c->homes_bytes = 0;
-        c->home_words = 0;
-        RT_TRY(c, hipMalloc(&c->d_homes, hb));
-        RT_TRY(c, hipMalloc(&c->d_home_bits, (size_t)words * sizeof(unsigned long long)));
-        // zero once: every wave returns the home it took, so a drained launch leaves the bitmap zero
-        RT_TRY(c, hipMemset(c->d_home_bits, 0, (size_t)words * sizeof(unsigned long long)));
-        c->homes_bytes = hb;
-        c->home_words = words;
-      }
-      ra.homes = c->d_homes;
-      ra.home_bits = c->d_home_bits;
-      ra.home_words = c->home_words;
-    }
-    // the sphere grids, lazily (sg_pending): the scene's first multi-frame
-    // launch or its second launch builds them, before the launch's timing
-    // (a speed-up: if its build fails the launch runs without the grids)
-    if (fast && kCull && c->sg_pending && (nf > 1 || c->scene_launches > 0)) {
-      if (sphere_grids(c) != RT_OK) {
+  // the default configuration (ordered 4-wide BVH walk, light grids) has kernels
+  // compiled with only those paths (kFast): no registers held for the others
+  sel.fast = merge && bv.ordered && bv.wide && lg.on;
+  // the light loop of sparse waves spread over the lanes (shade_hit kWide, the default)
+  sel.wide = sel.fast && (c->wide_mode >= 2 || (nf == 1 && c->wide_mode == 1));
+  const void *const kf = render_kernel_fn(sel);
+  if (merge && depth > 1) {  // the stack homes: 2 x the render kernel's resident waves
+    if (kf != c->occ_kernel || lds != c->occ_lds) {
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * kWg, lds) != hipSuccess || nb < 1) {
         (void)hipGetLastError();
-        c->err.clear();
-        c->sg_ok = false;
+        nb = 32;  // the most waves a CU holds
       }
+      c->occ_kernel = kf;
+      c->occ_lds = lds;
+      c->occ_blocks = nb;
     }
-    // the camera grids' host part (policy, tables, buffers) first; the
-    // launch's timing starts after it: the grids' device passes ahead of the
-    // render kernel are part of the launch
-    CgPlan plan;
-    if (fast && kCull) {
-      const int rc = cam_grid_prepare(c, cam, nf, plan);
-      if (rc != RT_OK) return rc;
+    const size_t words = (size_t)(((long long)2 * c->occ_blocks * kWg * c->n_cu + 63) / 64);
+    const size_t hb = words * 64 * (size_t)(depth - 1) * kHomePx * sizeof(StackEnt);
+    const size_t wb = words * sizeof(unsigned long long);
+    if (c->homes.bytes() < hb || c->home_bits.bytes() < wb) {
+      RT_TRY(c, hipStreamSynchronize(c->stream));  // launches in flight hold homes
+      c->homes.reset(), c->home_bits.reset();      // both go, whichever was too small
+      RT_TRY(c, c->homes.alloc(hb));
+      RT_TRY(c, c->home_bits.alloc(wb));
+      // zero once: every wave returns the home it took, so a drained launch leaves the bitmap zero
+      RT_TRY(c, hipMemset(c->home_bits.get(), 0, wb));
     }
-    RT_TRY(c, mark_start(c));
-    {
-      const int rc = cam_grid_enqueue(c, plan, ra.cg);
-      if (rc != RT_OK) return rc;
+    ra.homes = c->homes.get();
+    ra.home_bits = c->home_bits.get();
+    ra.home_words = (int)(c->home_bits.bytes() / sizeof(unsigned long long));
+  }
+  // the sphere grids, lazily (sg_pending): the scene's first multi-frame
+  // launch or its second launch builds them, before the launch's timing
+  // (a speed-up: if its build fails the launch runs without the grids)
+  if (sel.fast && sel.cull && scn.sg_pending && (nf > 1 || scn.launches > 0)) {
+    // an error of the launches in flight is theirs, not a failed build
+    RT_TRY(c, hipStreamSynchronize(c->stream));
+    if (sphere_grids(c) != RT_OK) {
+      (void)hipGetLastError();
+      c->err.clear();
+      scn.sg_ok = false;  // (nothing half-built to release: sphere_grids hands its buffers over only when complete)
     }
-    if (fast && kCull && c->sg_ok)
-      ra.sg = SgArgs{c->d_sg_start, c->d_sg_ent, c->d_sg_rho2, c->sg_n, 1, c->sg_nstart, c->sg_nent, c->nsph};
-    c->cg_last = ra.cg.on != 0;
-    c->cg_last_n = ra.cg.on ? ra.cg.N : 0;
-    if (wide)
-      hipLaunchKernelGGL((render_kernel<kLds, kCull, kSamples, kStack, true, true>), grid, dim3(64 * kWg), lds, c->stream,
-                         ra);
-    else if (fast)
-      hipLaunchKernelGGL((render_kernel<kLds, kCull, kSamples, kStack, true>), grid, dim3(64 * kWg), lds, c->stream, ra);
-    else
-      hipLaunchKernelGGL((render_kernel<kLds, kCull, kSamples, kStack>), grid, dim3(64 * kWg), lds, c->stream, ra);
-    if (ra.dq_cap > 0) {  // 48 one-wave workgroups per shard segment
-      // the walk kernel where every closest hit walks the BVH anyway (large
-      // scenes: synth10k 12.2 -> 11.0 ms per 8-frame launch); small scenes keep
-      // the cull sweeps (synth200 1 % slower on the walk kernel)
-      if (kCull && fast && c->defer_walk && bv.nnodes > 0 && bv.always && !(bv.ug.on && bv.ug.closest))
-        hipLaunchKernelGGL(render_deferred_walk, dim3(RT_DEFER_WGS * kShards), dim3(64), lds, c->stream, ra);
-      else if (fast && c->wide_mode == 3)  // the deferred waves' tails spread their light loops too
-        hipLaunchKernelGGL((render_deferred<kCull, true, true>), dim3(RT_DEFER_WGS * kShards), dim3(64), lds, c->stream,
-                           ra);
-      else if (fast)
-        hipLaunchKernelGGL((render_deferred<kCull, true>), dim3(RT_DEFER_WGS * kShards), dim3(64), lds, c->stream, ra);
-      else
-        hipLaunchKernelGGL((render_deferred<kCull>), dim3(RT_DEFER_WGS * kShards), dim3(64), lds, c->stream, ra);
-    }
-  } else {
-    RT_TRY(c, mark_start(c));
-    hipLaunchKernelGGL((render_kernel<kLds, kCull, kSamples, kStack>), grid, dim3(64 * kWg), lds, c->stream, ra);
-    if constexpr (kStack == kStackMerge) {
-      if (ra.dq_cap > 0)
-        hipLaunchKernelGGL((render_deferred<kCull>), dim3(RT_DEFER_WGS * kShards), dim3(64), lds, c->stream, ra);
-    }
+  }
+  // the camera grids' host part (policy, tables, buffers) first; the
+  // launch's timing starts after it: the grids' device passes ahead of the
+  // render kernel are part of the launch
+  CgPlan plan;
+  if (sel.fast && sel.cull) {
+    const int rc = cam_grid_prepare(c, cam, nf, plan);
+    if (rc != RT_OK) return rc;
+  }
+  RT_TRY(c, mark_start(c));
+  {
+    const int rc = cam_grid_enqueue(c, plan, ra.cg);
+    if (rc != RT_OK) return rc;
+  }
+  if (sel.fast && sel.cull && scn.sg_ok)
+    ra.sg = SgArgs{scn.sg_start.get(), scn.sg_ent.get(), scn.sg_rho2.get(), scn.sg_n, 1,
+                   scn.sg_nstart,      scn.sg_nent, scn.nsph};
+  c->cg_last = ra.cg.on != 0;
+  c->cg_last_n = ra.cg.on ? ra.cg.N : 0;
+  void *args[] = {&ra};
+  RT_TRY(c, hipLaunchKernel(kf, grid, dim3(64 * kWg), args, lds, c->stream));
+  if (ra.dq_cap > 0) {  // 48 one-wave workgroups per shard segment
+    // the walk kernel where every closest hit walks the BVH anyway (large
+    // scenes: synth10k 12.2 -> 11.0 ms per 8-frame launch); small scenes keep
+    // the cull sweeps (synth200 1 % slower on the walk kernel); else the
+    // deferred waves' tails spread their light loops too (wide_mode 3)
+    const bool walk = sel.cull && sel.fast && c->defer_walk && bv.nnodes > 0 && bv.always && !(bv.ug.on && bv.ug.closest);
+    RT_TRY(c, hipLaunchKernel(deferred_kernel_fn(sel, walk, sel.fast && c->wide_mode == 3),
+                              dim3(RT_DEFER_WGS * kShards), dim3(64), args, lds, c->stream));
   }
   return RT_OK;
 }
 
-template <bool kLds, bool kCull, int kSamples>
-int launch_render4(rt_ctx *c, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
-                   const OutDesc &od) {
-  if (c->stack_mode == kStackMerge) {
-    // merged reflection levels: RGB8 row-compact output, one sample, scene through L2,
-    // and only while the wave's LDS (BVH stacks + ray queue) still allows the
-    // 12 waves per CU its registers allow (synth10k's 22-entry stacks do not:
-    // 10 waves, 12 % slower); otherwise the per-pixel global stack
-    if constexpr (!kLds && kSamples == 1) {
-      const BvhArgs bv = bvh_args(c, cam);
-      const size_t stacks = bv.ordered ? (size_t)bv.odepth * 64 * sizeof(int2) : 0;
-      if (od.fmt == RT_FB_RGB8 && !od.full && od.x0 == 0 && od.xw == W)
-        for (int q = c->merge_q_max; q >= 8; q /= 2)  // the longest queue that keeps 12 waves per CU
-          if (12 * (stacks + (size_t)q * sizeof(QRay) + kPixbufBytes + ((lds + 31) & ~(size_t)31)) <= 160 * 1024) {
-            c->merge_q = q;
-            return launch_tiles<kLds, kCull, 1, kStackMerge>(c, lds, cam, W, H, depth, rows, od);
-          }
-    }
-    return launch_tiles<kLds, kCull, kSamples, kStackGlobal>(c, lds, cam, W, H, depth, rows, od);
-  }
-  return launch_tiles<kLds, kCull, kSamples, kStackGlobal>(c, lds, cam, W, H, depth, rows, od);
-}
-
 int launch_render(rt_ctx *c, bool lds_geo, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
                   const OutDesc &od) {
-  const bool aa = c->samples == 4;
-  if (lds_geo) {
-    if (c->cull) return aa ? launch_render4<true, true, 4>(c, lds, cam, W, H, depth, rows, od)
-                           : launch_render4<true, true, 1>(c, lds, cam, W, H, depth, rows, od);
-    return aa ? launch_render4<true, false, 4>(c, lds, cam, W, H, depth, rows, od)
-              : launch_render4<true, false, 1>(c, lds, cam, W, H, depth, rows, od);
+  KernelSel sel{lds_geo, c->cull, c->samples == 4 ? 4 : 1, kStackGlobal};
+  // merged reflection levels: RGB8 row-compact output, one sample, scene through L2,
+  // and only while the wave's LDS (BVH stacks + ray queue) still allows the
+  // 12 waves per CU its registers allow (synth10k's 22-entry stacks do not:
+  // 10 waves, 12 % slower); otherwise the per-pixel global stack
+  if (c->stack_mode == kStackMerge && !sel.lds && sel.samples == 1 && od.fmt == RT_FB_RGB8 && !od.full && od.x0 == 0 &&
+      od.xw == W) {
+    const BvhArgs bv = bvh_args(c, cam);
+    const size_t stacks = bv.ordered ? (size_t)bv.odepth * 64 * sizeof(int2) : 0;
+    for (int q = c->merge_q_max; q >= 8; q /= 2)  // the longest queue that keeps 12 waves per CU
+      if (12 * (stacks + (size_t)q * sizeof(QRay) + kPixbufBytes + ((lds + 31) & ~(size_t)31)) <= 160 * 1024) {
+        c->merge_q = q;
+        sel.stack = kStackMerge;
+        break;
+      }
   }
-  if (c->cull) return aa ? launch_render4<false, true, 4>(c, lds, cam, W, H, depth, rows, od)
-                         : launch_render4<false, true, 1>(c, lds, cam, W, H, depth, rows, od);
-  return aa ? launch_render4<false, false, 4>(c, lds, cam, W, H, depth, rows, od)
-            : launch_render4<false, false, 1>(c, lds, cam, W, H, depth, rows, od);
+  return launch_tiles(c, sel, lds, cam, W, H, depth, rows, od);
 }
 
 int validate(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows, const void *out,
              Rows &r) {
   if (!c || !cam || !out || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
-  if (!c->has_scene) return RT_ERR_NO_SCENE;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
   r = rows ? Rows{rows->band, rows->first, rows->stride, rows->count} : Rows{1, 0, 1, H};
   if (r.band < 1 || r.stride < 1 || r.first < 0 || r.count < 0) return RT_ERR_INVALID_ARG;
@@ -3136,7 +3199,7 @@ int validate(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_
 int enqueue(rt_ctx *c, const rt_camera *cm, int W, int H, int depth, const Rows &r, const OutDesc &od) {
   RT_TRY(c, hipSetDevice(c->device));
   const int half = (int)(c->launches & 1);
-  c->d_counters = c->d_ctr_base + (size_t)half * kShards * kShardStride;
+  c->d_counters = c->ctr_base.get() + (size_t)half * kShards * kShardStride;
   if (!c->ctr_clean[half])
     RT_TRY(c, hipMemsetAsync(c->d_counters, 0, kShards * kShardStride * sizeof(unsigned long long), c->stream));
   c->ctr_clean[half] = false;
@@ -3148,9 +3211,10 @@ int enqueue(rt_ctx *c, const rt_camera *cm, int W, int H, int depth, const Rows 
   if (r.count > 0) {
     const Cam cam = to_cam(*cm);
     // the scene and its BVH are staged in LDS when they fit (lds_layout)
-    const int nn = (c->bvh_on && c->cull) ? c->bvh_nodes : 0;
-    const bool lds_geo = c->lds_scene && lds_layout(true, c->nsph, c->nlight, nn).end <= kLdsBudget;
-    const size_t lds = lds_layout(lds_geo, c->nsph, c->nlight, nn).end;
+    const Scene &scn = c->scene;
+    const int nn = (c->bvh_on && c->cull) ? scn.bvh_nodes : 0;
+    const bool lds_geo = c->lds_scene && lds_layout(true, scn.nsph, scn.nlight, nn).end <= kLdsBudget;
+    const size_t lds = lds_layout(lds_geo, scn.nsph, scn.nlight, nn).end;
     if (lds > kLdsBudget) {
       c->err = "light list does not fit in LDS";
       return RT_ERR_INVALID_ARG;
@@ -3163,7 +3227,7 @@ int enqueue(rt_ctx *c, const rt_camera *cm, int W, int H, int depth, const Rows 
   if (c->zero_pending) c->ctr_clean[(c->launches + 1) & 1] = true;
   c->zero_pending = false;
   c->launches++;
-  c->scene_launches++;
+  c->scene.launches++;
   return RT_OK;  // the counters are read back by rt_render_stats, after the stream drains
 }
 
@@ -3244,14 +3308,13 @@ int rt_create(int device, rt_ctx **out) {
   if (hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault) != hipSuccess) return bail(RT_ERR_HIP);
   if (hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming) != hipSuccess) return bail(RT_ERR_HIP);
   c->stream = c->own_stream;
-  if (hipMalloc(&c->d_ctr_base, 2 * kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
+  if (c->ctr_base.alloc(2 * kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
     return bail(RT_ERR_OUT_OF_MEMORY);
-  if (hipMemset(c->d_ctr_base, 0, 2 * kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
-    return bail(RT_ERR_HIP);
-  c->d_counters = c->d_ctr_base;
-  if (hipHostMalloc(&c->h_counters, kShards * kShardStride * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+  if (hipMemset(c->ctr_base.get(), 0, c->ctr_base.bytes()) != hipSuccess) return bail(RT_ERR_HIP);
+  c->d_counters = c->ctr_base.get();
+  if (c->h_counters.alloc(kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
     return bail(RT_ERR_OUT_OF_MEMORY);
-  std::memset(c->h_counters, 0, kShards * kShardStride * sizeof(unsigned long long));
+  std::memset(c->h_counters.get(), 0, c->h_counters.bytes());
   for (int i = 0; i < rt_ctx::kRing; i++)
     if (hipEventCreate(&c->ev0[i]) != hipSuccess || hipEventCreate(&c->ev1[i]) != hipSuccess) return bail(RT_ERR_HIP);
   // The HIP runtime's one-time work in a process, done here rather than
@@ -3267,7 +3330,7 @@ int rt_create(int device, rt_ctx **out) {
     std::lock_guard<std::mutex> lk(warm_mu);
     if (std::find(warmed.begin(), warmed.end(), device) == warmed.end()) {
       hipFuncAttributes fa;
-      (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&render_kernel<false, true, 1, kStackMerge, true, true>));
+      (void)hipFuncGetAttributes(&fa, render_kernel_fn(KernelSel{false, true, 1, kStackMerge, true, true}));  // the default
       std::vector<unsigned char> h((size_t)1 << 20);
       void *d = nullptr;
       if (hipMalloc(&d, h.size()) == hipSuccess) {
@@ -3290,36 +3353,13 @@ void rt_destroy(rt_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
-  free_scene(c);
-  if (c->d_ctr_base) (void)hipFree(c->d_ctr_base);
-  if (c->h_counters) (void)hipHostFree(c->h_counters);
-  if (c->d_tmp) (void)hipFree(c->d_tmp);
-  if (c->cstack_buf) (void)hipFree(c->cstack_buf);
-  if (c->dq_buf) (void)hipFree(c->dq_buf);
-  if (c->d_homes) (void)hipFree(c->d_homes);
-  if (c->d_home_bits) (void)hipFree(c->d_home_bits);
-  if (c->d_perm) (void)hipFree(c->d_perm);
-  if (c->h_perm) (void)hipHostFree(c->h_perm);
-  if (c->d_bperm) (void)hipFree(c->d_bperm);
-  if (c->h_bperm) (void)hipHostFree(c->h_bperm);
-  if (c->d_cg_count) (void)hipFree(c->d_cg_count);
-  if (c->d_cg_ent) (void)hipFree(c->d_cg_ent);
-  if (c->d_cg_disks) (void)hipFree(c->d_cg_disks);
-  if (c->d_cg_pairs) (void)hipFree(c->d_cg_pairs);
-  if (c->d_cg_npairs) (void)hipFree(c->d_cg_npairs);
-  for (auto &t : c->cg_tab) {
-    if (t.faces) (void)hipFree(t.faces);
-    if (t.blocks) (void)hipFree(t.blocks);
-    if (t.tiles) (void)hipFree(t.tiles);
-    if (t.cell) (void)hipFree(t.cell);
-  }
   for (int i = 0; i < rt_ctx::kRing; i++) {
     if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
     if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
   }
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // the buffers free themselves
 }
 
 const char *rt_last_error(const rt_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -3345,6 +3385,74 @@ int rt_set_culling(rt_ctx *c, int enable) {
   return RT_OK;
 }
 
+// The device half of rt_upload_scene: the staged arrays to the device, then
+// the grids that are built there.  The caller frees the scene on an error.
+static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool want_ug) {
+  Scene &scn = c->scene;
+  const int n = s->num_spheres;
+  const auto t_bvh = std::chrono::steady_clock::now();
+  RT_TRY(c, scn.bvh2.upload(st.nodes2, 1));
+  RT_TRY(c, scn.bvh4.upload(st.nodes4, 1));
+  RT_TRY(c, scn.pf.upload(st.pf, 1));
+  RT_TRY(c, scn.bvh.upload(st.nodes, 1));
+  RT_TRY(c, scn.prims.upload(st.prims, 1));
+  c->bvh_build_ms = st.bvh_ms + ms_since(t_bvh);
+  if (want_ug) {
+    const auto t_ug = std::chrono::steady_clock::now();
+    if (st.ug_built) {
+      const UgridHost &ug = st.ug;
+      RT_TRY(c, scn.ug_rec.upload(ug.rec));
+      RT_TRY(c, scn.ug_rid.upload(ug.rid));
+      RT_TRY(c, scn.ug_q.upload(ug.q));
+      RT_TRY(c, scn.ug_ids.upload(ug.ids, 1));
+      RT_TRY(c, scn.ug_glob.upload(ug.glob, 1));
+      scn.ug = UgArgs{reinterpret_cast<const float4 *>(scn.ug_rec.get()), scn.ug_rid.get(),
+                      reinterpret_cast<const float4 *>(scn.ug_q.get()), scn.ug_ids.get(), scn.ug_glob.get(),
+                      (int)ug.glob.size(), ug.nx, ug.ny, ug.nz, ug.gx, ug.gy, ug.gz, ug.cs, 0, 0,
+                      (float)(1e-4 * (double)ug.extent), (int)ug.q.size()};
+      scn.ug_reg_margin = ug.reg_margin;
+      scn.ug_extent = ug.extent;
+      scn.ug_entries = ug.ids.size();
+      scn.ug_ok = true;
+    }
+    c->ug_build_ms = st.ug_ms + ms_since(t_ug);
+  }
+  scn.bvh_nodes = (int)st.nodes.size();
+  scn.bvh2_nodes = (int)st.nodes2.size();
+  scn.bvh4_nodes = (int)st.nodes4.size();
+  scn.bvh_prims = (int)st.prims.size();
+  scn.bvh2_root = st.root2;
+  scn.bvh_depth = st.depth2;
+  scn.bvh4_root = st.root4;
+  scn.bvh4_stack = st.stack4;
+  for (int k = 0; k < 3; k++) {
+    scn.c0[k] = st.c0[k];
+    scn.lo[k] = st.lo[k];
+    scn.hi[k] = st.hi[k];
+  }
+  scn.rmax = st.rmax;
+  RT_TRY(c, scn.geo.upload(st.geo, 1));
+  RT_TRY(c, scn.rad.upload(st.rad, 1));
+  RT_TRY(c, scn.mat.upload(st.mat, 1));
+  RT_TRY(c, scn.lights.upload(st.lights, 1));
+  // built on the device from geo / rad
+  c->nsph_up = n;
+  int rc = light_grids(c, s, st);
+  if (rc != RT_OK) return rc;
+  // the spheres' copy only where a grid may be built from it, until it has been
+  const bool sg_auto = c->sg_mode < 0 && n <= kSgMaxSpheres;
+  if (c->sg_mode > 0 || sg_auto) scn.sg_src.assign(s->spheres, s->spheres + n);
+  scn.sg_diam = st.diam;
+  scn.launches = 0;
+  scn.sg_pending = sg_auto;
+  if (c->sg_mode > 0 && (rc = sphere_grids(c)) != RT_OK) return rc;
+  scn.nsph = n;
+  scn.nlight = s->num_lights;
+  scn.refl = std::move(st.refl);
+  for (int q = 0; q < 3; q++) scn.amb[q] = s->ambient[q];
+  return RT_OK;
+}
+
 int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   if (!c || !s || s->num_spheres < 0 || s->num_lights < 0) return RT_ERR_INVALID_ARG;
   if ((s->num_spheres > 0 && !s->spheres) || (s->num_lights > 0 && !s->lights)) return RT_ERR_INVALID_ARG;
@@ -3352,194 +3460,23 @@ int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   RT_TRY(c, hipSetDevice(c->device));
   RT_TRY(c, hipStreamSynchronize(c->stream));
   free_scene(c);
-  const int n = s->num_spheres, nl = s->num_lights;
-  SphGeo *hg = new SphGeo[n + 1];
-  double *hr = new double[n + 1];
-  SphMat *hm = new SphMat[n + 1];
-  LightD *hl = new LightD[nl + 1];
-  for (int i = 0; i < n; i++) {
-    const rt_sphere &sp = s->spheres[i];
-    hg[i] = SphGeo{sp.center[0], sp.center[1], sp.center[2], sp.radius * sp.radius};
-    hr[i] = sp.radius < 0 ? -sp.radius : sp.radius;
-    hm[i] = SphMat{sp.color[0], sp.color[1], sp.color[2], sp.reflectivity, sp.shininess, 0.0};
-  }
-  for (int i = 0; i < nl; i++) {
-    const rt_light &L = s->lights[i];
-    hl[i] = LightD{L.position[0], L.position[1], L.position[2], L.color[0], L.color[1], L.color[2]};
-  }
-  // scene bounds (spheres and lights), centre, largest radius; BVH relative to the centre
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, rmax = 0.0;
-  auto grow = [&](const double *p, double r) {
-    for (int k = 0; k < 3; k++) {
-      lo[k] = std::min(lo[k], p[k] - r);
-      hi[k] = std::max(hi[k], p[k] + r);
-    }
-  };
-  for (int i = 0; i < n; i++) {
-    const double r = std::fabs(s->spheres[i].radius);
-    grow(s->spheres[i].center, r);
-    if (r > rmax || r != r) rmax = r != r ? INFINITY : r;
-  }
-  for (int i = 0; i < nl; i++) grow(s->lights[i].position, 0.0);
-  double c0[3] = {0, 0, 0};
-  if (n + nl > 0)
-    for (int k = 0; k < 3; k++) c0[k] = std::isfinite(lo[k] + hi[k]) ? 0.5 * (lo[k] + hi[k]) : 0.0;
-  std::vector<double> bx(n), by(n), bz(n), br(n);
-  for (int i = 0; i < n; i++) {
-    bx[i] = s->spheres[i].center[0] - c0[0];
-    by[i] = s->spheres[i].center[1] - c0[1];
-    bz[i] = s->spheres[i].center[2] - c0[2];
-    br[i] = s->spheres[i].radius;
-  }
-  const bool big = n > kBvhAlwaysAbove;
-  const auto t_bvh = std::chrono::steady_clock::now();
+  const bool big = s->num_spheres > kBvhAlwaysAbove;
   // leaves of 2 spheres (+0.6..0.9 % over 4 on synth200 with the merged levels);
   // 1 above kBvhAlwaysAbove, where every closest hit walks (synth10k 4.37 -> 4.16 ms)
   c->bvh_leaf = c->bvh_leaf_opt ? c->bvh_leaf_opt : (big ? 1 : 2);
   c->lg_n = c->lg_n_opt ? c->lg_n_opt : (big ? 768 : 128);
-  std::vector<BvhNode> nodes;
-  std::vector<int32_t> prims;
-  build_bvh(bx.data(), by.data(), bz.data(), br.data(), n, c->bvh_leaf, nodes, prims);
-  // prefilter records in leaf order (centre - c0 in fp32, |radius| rounded up)
-  std::vector<float4> pf(prims.size());
-  for (size_t k = 0; k < prims.size(); k++) {
-    const int id = prims[k];
-    float rr = (float)std::fabs(br[id]);
-    if ((double)rr < std::fabs(br[id])) rr = std::nextafter(rr, INFINITY);
-    pf[k] = make_float4((float)bx[id], (float)by[id], (float)bz[id], rr);
-  }
-  std::vector<BvhNode2> nodes2;
-  int depth2 = 0;
-  const int32_t root2 = build_bvh2(nodes, nodes2, depth2);
-  std::vector<BvhNode4> nodes4;
-  int stack4 = 0;
-  const int32_t root4 = build_bvh4(nodes, nodes4, stack4);
-  int rc = RT_OK;
-  hipError_t e = hipSuccess;
-  if ((e = hipMalloc(&c->d_bvh2, sizeof(BvhNode2) * (nodes2.size() + 1))) != hipSuccess ||
-      (e = hipMalloc(&c->d_bvh4, sizeof(BvhNode4) * (nodes4.size() + 1))) != hipSuccess ||
-      (!nodes4.empty() && (e = hipMemcpy(c->d_bvh4, nodes4.data(), sizeof(BvhNode4) * nodes4.size(),
-                                         hipMemcpyHostToDevice)) != hipSuccess) ||
-      (!nodes2.empty() && (e = hipMemcpy(c->d_bvh2, nodes2.data(), sizeof(BvhNode2) * nodes2.size(),
-                                         hipMemcpyHostToDevice)) != hipSuccess) ||
-      (e = hipMalloc(&c->d_pf, sizeof(float4) * (pf.size() + 1))) != hipSuccess ||
-      (!pf.empty() && (e = hipMemcpy(c->d_pf, pf.data(), sizeof(float4) * pf.size(), hipMemcpyHostToDevice)) !=
-                          hipSuccess) ||
-      (e = hipMalloc(&c->d_bvh, sizeof(BvhNode) * (nodes.size() + 1))) != hipSuccess ||
-      (e = hipMalloc(&c->d_prims, sizeof(int32_t) * (prims.size() + 1))) != hipSuccess ||
-      (!nodes.empty() &&
-       (e = hipMemcpy(c->d_bvh, nodes.data(), sizeof(BvhNode) * nodes.size(), hipMemcpyHostToDevice)) != hipSuccess) ||
-      (!prims.empty() &&
-       (e = hipMemcpy(c->d_prims, prims.data(), sizeof(int32_t) * prims.size(), hipMemcpyHostToDevice)) != hipSuccess)) {
-    rc = fail(c, e, "rt_upload_scene(bvh)");
+  const bool want_ug = c->ug_mode > 0 || (c->ug_mode < 0 && big);
+  StagedScene st;
+  stage_scene(s, c->bvh_leaf, want_ug, c->ug_cells, st);
+  const int rc = upload_staged(c, s, st, want_ug);
+  if (rc != RT_OK) {
     free_scene(c);
-    delete[] hg;
-    delete[] hr;
-    delete[] hm;
-    delete[] hl;
     return rc;
   }
-  c->bvh_build_ms = ms_since(t_bvh);
-  if (c->ug_mode > 0 || (c->ug_mode < 0 && big)) {
-    const auto t_ug = std::chrono::steady_clock::now();
-    UgridHost ug;
-    if (build_ugrid(bx.data(), by.data(), bz.data(), br.data(), n, kUgMaxEntries, ug, c->ug_cells)) {
-      if ((e = hipMalloc(&c->d_ug_rec, sizeof(UgRec) * ug.rec.size())) != hipSuccess ||
-          (e = hipMalloc(&c->d_ug_rid, sizeof(int32_t) * ug.rid.size())) != hipSuccess ||
-          (e = hipMalloc(&c->d_ug_q, sizeof(UgRec) * ug.q.size())) != hipSuccess ||
-          (e = hipMalloc(&c->d_ug_ids, sizeof(int32_t) * (ug.ids.size() + 1))) != hipSuccess ||
-          (e = hipMalloc(&c->d_ug_glob, sizeof(int32_t) * (ug.glob.size() + 1))) != hipSuccess ||
-          (e = hipMemcpy(c->d_ug_rec, ug.rec.data(), sizeof(UgRec) * ug.rec.size(), hipMemcpyHostToDevice)) !=
-              hipSuccess ||
-          (e = hipMemcpy(c->d_ug_rid, ug.rid.data(), sizeof(int32_t) * ug.rid.size(), hipMemcpyHostToDevice)) !=
-              hipSuccess ||
-          (e = hipMemcpy(c->d_ug_q, ug.q.data(), sizeof(UgRec) * ug.q.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-          (!ug.ids.empty() && (e = hipMemcpy(c->d_ug_ids, ug.ids.data(), sizeof(int32_t) * ug.ids.size(),
-                                             hipMemcpyHostToDevice)) != hipSuccess) ||
-          (!ug.glob.empty() && (e = hipMemcpy(c->d_ug_glob, ug.glob.data(), sizeof(int32_t) * ug.glob.size(),
-                                              hipMemcpyHostToDevice)) != hipSuccess)) {
-        rc = fail(c, e, "rt_upload_scene(uniform grid)");
-        free_scene(c);
-        delete[] hg;
-        delete[] hr;
-        delete[] hm;
-        delete[] hl;
-        return rc;
-      }
-      c->ug = UgArgs{reinterpret_cast<const float4 *>(c->d_ug_rec), c->d_ug_rid,
-                     reinterpret_cast<const float4 *>(c->d_ug_q), c->d_ug_ids, c->d_ug_glob, (int)ug.glob.size(),
-                     ug.nx, ug.ny, ug.nz, ug.gx, ug.gy, ug.gz, ug.cs, 0, 0, (float)(1e-4 * (double)ug.extent),
-                     (int)ug.q.size()};
-      c->ug_reg_margin = ug.reg_margin;
-      c->ug_extent = ug.extent;
-      c->ug_entries = ug.ids.size();
-      c->ug_ok = true;
-    }
-    c->ug_build_ms = ms_since(t_ug);
-  }
-  c->bvh_nodes = (int)nodes.size();
-  c->bvh2_nodes = (int)nodes2.size();
-  c->bvh4_nodes = (int)nodes4.size();
-  c->bvh_prims = (int)prims.size();
-  c->bvh2_root = root2;
-  c->bvh_depth = depth2;
-  c->bvh4_root = root4;
-  c->bvh4_stack = stack4;
-  double scene_diam = 0.0;
-  {
-    double d2 = 0.0;
-    for (int k = 0; k < 3; k++) d2 += (hi[k] - lo[k]) * (hi[k] - lo[k]);
-    const double diam = n + nl > 0 ? std::sqrt(d2) : 0.0;
-    std::vector<double> sx(n), sy(n), sz(n);
-    for (int i = 0; i < n; i++) {
-      sx[i] = s->spheres[i].center[0];
-      sy[i] = s->spheres[i].center[1];
-      sz[i] = s->spheres[i].center[2];
-    }
-    c->h_sx = sx;
-    c->h_sy = sy;
-    c->h_sz = sz;
-    c->h_sr = br;
-    scene_diam = diam;
-  }
-  for (int k = 0; k < 3; k++) {
-    c->c0[k] = c0[k];
-    c->lo[k] = lo[k];
-    c->hi[k] = hi[k];
-  }
-  c->rmax = rmax;
-  if ((e = hipMalloc(&c->d_geo, sizeof(SphGeo) * (n + 1))) != hipSuccess ||
-      (e = hipMalloc(&c->d_rad, sizeof(double) * (n + 1))) != hipSuccess ||
-      (e = hipMalloc(&c->d_mat, sizeof(SphMat) * (n + 1))) != hipSuccess ||
-      (e = hipMalloc(&c->d_lights, sizeof(LightD) * (nl + 1))) != hipSuccess ||
-      (e = hipMemcpy(c->d_geo, hg, sizeof(SphGeo) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_rad, hr, sizeof(double) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_mat, hm, sizeof(SphMat) * n, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(c->d_lights, hl, sizeof(LightD) * nl, hipMemcpyHostToDevice)) != hipSuccess) {
-    rc = fail(c, e, "rt_upload_scene");
-    free_scene(c);
-  } else if ((c->nsph_up = n, rc = light_grids(c, s, scene_diam)) != RT_OK ||  // built on the device from d_geo /
-             (c->sg_src.assign(s->spheres, s->spheres + n), c->sg_diam = scene_diam, c->scene_launches = 0,
-              c->sg_pending = c->sg_mode < 0, rc = c->sg_mode > 0 ? sphere_grids(c) : RT_OK) != RT_OK) {  // d_rad
-    free_scene(c);
-  } else {
-    c->nsph = n;
-    c->nlight = nl;
-    c->h_refl.clear();
-    for (int i = 0; i < n; i++)
-      if (s->spheres[i].reflectivity > 0.0)  // main.cpp:43
-        c->h_refl.push_back(SchedSphere{s->spheres[i].center[0], s->spheres[i].center[1], s->spheres[i].center[2],
-                                        s->spheres[i].radius});
-    c->scene_gen++;
-    for (int q = 0; q < 3; q++) c->amb[q] = s->ambient[q];
-    c->has_scene = true;
-    c->upload_ms = ms_since(t_upload);
-  }
-  delete[] hg;
-  delete[] hr;
-  delete[] hm;
-  delete[] hl;
-  return rc;
+  c->scene_gen++;
+  c->scene.has_scene = true;
+  c->upload_ms = ms_since(t_upload);
+  return RT_OK;
 }
 
 int rt_render_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows, uint8_t *out) {
@@ -3574,11 +3511,11 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
     const int slot = (int)((c->launches - 1) % rt_ctx::kRing);
     RT_TRY(c, hipEventElapsedTime(&ms, c->ev0[slot], c->ev1[slot]));
   }
-  RT_TRY(c, hipMemcpy(c->h_counters, c->d_counters, kShards * kShardStride * sizeof(unsigned long long),
-                      hipMemcpyDeviceToHost));
+  const unsigned long long *hc = c->h_counters.get();
+  RT_TRY(c, hipMemcpy(c->h_counters.get(), c->d_counters, c->h_counters.bytes(), hipMemcpyDeviceToHost));
   unsigned long long sum[kCounters] = {};
   for (int sh = 0; sh < kShards; sh++)
-    for (int q = 0; q < kCounters; q++) sum[q] += c->h_counters[sh * kShardStride + q];
+    for (int q = 0; q < kCounters; q++) sum[q] += hc[sh * kShardStride + q];
   st->rays_primary = sum[0];
   st->rays_shadow = sum[1];
   st->rays_reflect = sum[2];
@@ -3622,18 +3559,18 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
   if (std::getenv("RT_HIP_STAMPS")) {  // diagnostic builds (-DRT_STAMPS) fill slots 8..14
     unsigned long long d[12] = {};
     for (int sh = 0; sh < kShards; sh++)
-      for (int q = 0; q < 12; q++) d[q] += c->h_counters[sh * kShardStride + 8 + q];
+      for (int q = 0; q < 12; q++) d[q] += hc[sh * kShardStride + 8 + q];
     const double nw = (double)(d[6] ? d[6] : 1);
     unsigned long long bvh = 0;
-    for (int sh = 0; sh < kShards; sh++) bvh += c->h_counters[sh * kShardStride + 20];
+    for (int sh = 0; sh < kShards; sh++) bvh += hc[sh * kShardStride + 20];
     std::fprintf(stderr,
                  "RT_STAMPS per wave: candidate iterations %.1f (closest %.1f, of which primary %.1f), sweeps %.2f "
                  "(closest %.2f), bvh cycles %.0f\n",
                  d[7] / nw, d[9] / nw, d[11] / nw, d[8] / nw, d[10] / nw, bvh / nw);
     unsigned long long cl = 0, sh = 0;
     for (int s2 = 0; s2 < kShards; s2++) {
-      cl += c->h_counters[s2 * kShardStride + 21];
-      sh += c->h_counters[s2 * kShardStride + 22];
+      cl += hc[s2 * kShardStride + 21];
+      sh += hc[s2 * kShardStride + 22];
     }
     std::fprintf(stderr, "RT_STAMPS cycles/wave: closest hits %.0f, shadow queries %.0f\n", cl / nw, sh / nw);
     std::fprintf(stderr, "RT_STAMPS waves=%llu cycles/wave: bound %.0f cull %.0f cand %.0f setup %.0f shade %.0f total %.0f\n",
@@ -3655,15 +3592,9 @@ int rt_render(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt
   size_t bytes = (size_t)r.count * W * 3;
   uint8_t *dst = out;
   if (!out_on_device) {
-    if (c->tmp_bytes < bytes) {
-      RT_TRY(c, hipStreamSynchronize(c->stream));
-      if (c->d_tmp) (void)hipFree(c->d_tmp);
-      c->d_tmp = nullptr;
-      c->tmp_bytes = 0;
-      RT_TRY(c, hipMalloc(&c->d_tmp, bytes ? bytes : 1));
-      c->tmp_bytes = bytes;
-    }
-    dst = c->d_tmp;
+    rc = grow(c, c->tmp, bytes);
+    if (rc != RT_OK) return rc;
+    dst = c->tmp.get();
   }
   rc = enqueue(c, cam, W, H, depth, r, OutDesc{dst, RT_FB_RGB8, 0, 0, W});
   if (rc != RT_OK) return rc;
@@ -3684,7 +3615,7 @@ int rt_render_tile(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, int
   if (!c || !cam || !fb_device || W <= 0 || H <= 0 || tile_w < 0 || tile_h < 0 || tile_x < 0 || tile_y < 0)
     return RT_ERR_INVALID_ARG;
   if (fb_format != RT_FB_RGB8 && fb_format != RT_FB_F32X3 && fb_format != RT_FB_F64X3) return RT_ERR_INVALID_ARG;
-  if (!c->has_scene) return RT_ERR_NO_SCENE;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
   // the reference kernel clips the tile to the image (kernel.cu:103)
   const int xe = (int)std::min<long long>(W, (long long)tile_x + tile_w);  // 64-bit: no overflow near INT_MAX
@@ -3702,7 +3633,7 @@ int rt_render_tiles(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, co
   if (fb_format != RT_FB_RGB8 && fb_format != RT_FB_F32X3 && fb_format != RT_FB_F64X3) return RT_ERR_INVALID_ARG;
   for (int i = 0; i < ntiles; i++)
     if (tiles[i].x < 0 || tiles[i].y < 0 || tiles[i].width < 0 || tiles[i].height < 0) return RT_ERR_INVALID_ARG;
-  if (!c->has_scene) return RT_ERR_NO_SCENE;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
   RT_TRY(c, hipSetDevice(c->device));
   c->req_tiles = tiles;
@@ -3742,20 +3673,20 @@ int rt_get_info(rt_ctx *c, rt_info *out) {
   out->tile_order_build_ms = c->perm_build_ms;
   out->upload_ms = c->upload_ms;
   out->launches = (uint64_t)c->launches;
-  out->sphere_grids = c->sg_ok ? c->sg_grids : 0;
-  out->sphere_grid_n = c->sg_ok ? c->sg_n : 0;
-  out->sphere_grid_entries = c->sg_ok ? (uint64_t)c->sg_entries : 0;
+  const Scene &scn = c->scene;
+  out->sphere_grids = scn.sg_ok ? scn.sg_grids : 0;
+  out->sphere_grid_n = scn.sg_ok ? scn.sg_n : 0;
+  out->sphere_grid_entries = scn.sg_ok ? (uint64_t)scn.sg_entries : 0;
   out->sphere_grid_build_ms = c->sg_build_ms;
-  out->behind_grid = c->ug_ok ? 1 : 0;
+  out->behind_grid = scn.ug_ok ? 1 : 0;
   out->behind_grid_last = c->ug_last ? 1 : 0;
-  out->behind_grid_cells = c->ug_ok ? (uint64_t)c->ug.nx * (uint64_t)c->ug.ny * (uint64_t)c->ug.nz : 0;
-  out->behind_grid_entries = c->ug_ok ? (uint64_t)c->ug_entries : 0;
+  out->behind_grid_cells = scn.ug_ok ? (uint64_t)scn.ug.nx * (uint64_t)scn.ug.ny * (uint64_t)scn.ug.nz : 0;
+  out->behind_grid_entries = scn.ug_ok ? (uint64_t)scn.ug_entries : 0;
   out->behind_grid_build_ms = c->ug_build_ms;
   out->bvh_build_ms = c->bvh_build_ms;
   out->light_grid_build_ms = c->lg_build_ms;
-  out->scratch_bytes = (uint64_t)(c->cstack_bytes + c->dq_bytes + c->homes_bytes +
-                                  (size_t)c->home_words * sizeof(unsigned long long) + c->cg_count_cap + c->cg_ent_cap +
-                                  c->cg_disks_cap + c->cg_pairs_cap + c->cg_npairs_cap + c->perm_cap);
+  out->scratch_bytes = (uint64_t)(c->gstack.bytes() + c->dq.bytes() + c->homes.bytes() + c->home_bits.bytes() +
+                                  c->cg_bytes() + c->perm.bytes());
   out->shadow_line_bounded = c->lg_off_free ? 1 : 0;
   out->reserved0 = 0;
   return RT_OK;

@@ -194,8 +194,12 @@ int rt_render(rt_ctx *ctx, const rt_camera *cam, int width, int height, int dept
  *     size is used.  The camera grids themselves (closest hits of camera rays)
  *     are built on the device ahead of the render kernel, per camera position,
  *     for a multi-frame launch (one grid per distinct position) or a one-frame
- *     launch at the previous launch's position (~0.05 ms, cached).
- * rt_get_info() reports both.  rt_render_stats() waits for the stream and
+ *     launch at the previous launch's position (~0.05 ms, cached);
+ *   - the sphere grids (closest hits of reflection rays; scenes of up to 2048
+ *     spheres), built once per uploaded scene by its first multi-frame launch
+ *     or its second launch: the call drains the stream, then builds them on
+ *     the device and waits (~2 ms).
+ * rt_get_info() reports all three.  rt_render_stats() waits for the stream and
  * returns the stats of the most recent rt_render_async. */
 int rt_render_async(rt_ctx *ctx, const rt_camera *cam, int width, int height, int depth, const rt_rows *rows,
                     uint8_t *rgb_out_device);
