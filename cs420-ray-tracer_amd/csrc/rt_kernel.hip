@@ -1,13 +1,15 @@
 // rt_kernel.hip -- gfx950 (MI355X / CDNA4) render loop + device half of the C-ABI.
 //
-// One lane per pixel, wave64 over an 8x8 pixel tile, 256-thread workgroups
-// (2x2 waves = 16x16 pixels).  Sphere geometry (cx,cy,cz,r*r as fp64, 32 B) and
-// the light list are staged into LDS per workgroup and read as wave-uniform
-// broadcasts; materials (48 B) are read from global memory only on a hit.
-// Shadow rays exit early once no lane of the wave is still unoccluded
-// (__ballot).  Reflections are walked iteratively; each level's
-// (shade*(1-refl), refl) is pushed on a per-lane stack and unwound at the end,
-// which reproduces the reference recursion's rounding exactly.
+// One lane per pixel, wave64 over an 8x8 pixel tile, one-wave workgroups; a
+// wave takes four tiles (merge_tiles; the heaviest and the last tiles of a
+// launch one each) in the host's heavy-first order.  The scene (spheres as
+// cx,cy,cz,r*r in fp64, lights, 4-wide BVH, light / camera / sphere / behind
+// grids) is read through L1/L2.  Reflections are walked iteratively: the rays
+// of a level are merged across the wave's tiles into full passes (an LDS
+// queue), deep levels of multi-frame launches go to a second kernel
+// (render_deferred), and each level's (shade*(1-refl), refl) is unwound at the
+// end, which reproduces the reference recursion's rounding exactly.
+// RT_HIP_LDS_SCENE=1 is the first design: 2x2-wave workgroups, scene in LDS.
 //
 // Numerics follow the serial fp64 path operation by operation:
 // vec3.h:13-33, ray.h:12, camera.h:17-25, sphere.h:26-64, scene.h:41-121,
@@ -1911,9 +1913,13 @@ struct Scene {
   int bvh2_root = -1, bvh_depth = 0, bvh4_root = -1, bvh4_stack = 0;
   int bvh_nodes = 0;
   int bvh2_nodes = 0, bvh4_nodes = 0, bvh_prims = 0;  // sizes the RT_CHECK build checks node / leaf indices against
+  int bvh_leaf = 4;  // spheres per leaf it was built with (Knobs::bvh_leaf_opt, rt_upload_scene)
   // per-light direction grids for shadow rays (rt_lightgrid.h)
   DevBuf<int32_t> lg_start, lg_ids;
   long long lg_nstart = 0, lg_nids = 0;
+  int lg_n = 128;  // their cells per cube-map face edge (Knobs::lg_n_opt, rt_upload_scene)
+  double lg_max_off = 0.0;
+  bool lg_off_free = false;  // shadow queries skip the per-ray max_off check (light_grids)
   // sphere grids (rt_lightgrid.h build_sphere_grids): the closest hit of
   // reflection rays in the kFast kernels, for the reflective spheres
   DevBuf<int32_t> sg_start;
@@ -1941,52 +1947,22 @@ struct Scene {
   size_t ug_entries = 0;
 };
 
-struct rt_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t switch_ev = nullptr;  // rt_set_stream: orders the new stream after the old one
-  Scene scene;
-  bool cull = true;
+// What rt_create reads from the environment (read_knobs), constant afterwards.
+// The product build reads RT_HIP_LDS_SCENE and RT_HIP_CAM_GRID; the tuning build
+// (-DRT_TUNING: variants/librt_hip_tuning.so) also the layout and grid knobs that the parity
+// tests sweep and the A/B scripts measured.  Every default is the measured optimum.
+struct Knobs {
   int bvh_ordered = 1;  // RT_HIP_BVH_ORDERED
   int bvh_wide = 1;     // RT_HIP_BVH4
-  int lg_n = 128, lg_on = 1;  // lg_n: the grid of the uploaded scene
-  int lg_n_opt = 0;            // RT_HIP_SHADOW_GRID_N; 0 = 128, or 768 above kBvhAlwaysAbove spheres
-  double lg_max_off = 0.0;
-  bool lg_off_free = false;  // shadow queries skip the per-ray max_off check (light_grids)
-  // camera grids (rt_device.h CgArgs), built on the device per camera
-  // position of a launch (cg_bin_kernel / cg_sort_kernel) and kept while the
-  // positions and the scene stay the same
+  int lg_on = 1;        // RT_HIP_SHADOW_GRID
+  int lg_n_opt = 0;     // RT_HIP_SHADOW_GRID_N; 0 = 128, or 768 above kBvhAlwaysAbove spheres
   int cg_mode = 1;    // RT_HIP_CAM_GRID: 0 off, 1 auto (a one-frame launch at a new position sweeps), 2 every launch
   int cg_n_opt = 0;   // RT_HIP_CAM_GRID_N (tuning build); 0 = kCgNStatic / kCgNMoving
   long long cg_budget_opt = -1;  // RT_HIP_CAM_GRID_BUDGET (tuning build): bytes for a launch's grids; -1 = kCgBudgetBytes
   long long cg_maxp_opt = -1;    // RT_HIP_CAM_GRID_MAXP (tuning build): pairs per grid kept; -1 = the pair budget
-  DevBuf<int32_t> cg_count;
-  DevBuf<int2> cg_ent;
-  DevBuf<CgDisk> cg_disks;
-  DevBuf<int2> cg_pairs;
-  DevBuf<unsigned> cg_npairs;
-  size_t cg_bytes() const {
-    return cg_count.bytes() + cg_ent.bytes() + cg_disks.bytes() + cg_pairs.bytes() + cg_npairs.bytes();
-  }
-  int cg_n = 0, cg_ngrid = 0;
-  std::vector<double> cg_pos;          // the grids' points (3 per grid)
-  std::vector<double> cg_seen;         // the previous launch's camera positions
-  unsigned long long cg_seen_gen = ~0ull;
-  unsigned long long cg_gen = ~0ull;   // scene_gen they were built for
-  struct CgTables {                    // the cube map's patch tables of one N on the device
-    int N = 0, NT = 0, NB = 0;
-    DevBuf<CubePatch> faces, blocks, tiles;
-    DevBuf<double> cell;
-  };
-  CgTables cg_tab[2];
-  int cg_tab_next = 0;
   // sphere grids (Scene::sg_*)
   int sg_mode = -1;  // RT_HIP_SPHERE_GRID: -1 auto (scenes of up to kSgMaxSpheres spheres), 0 off, 1 on
   int sg_n_opt = 0;  // RT_HIP_SPHERE_GRID_N; 0 = kSgN
-  double sg_build_ms = 0.0;
-  double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds (rt_info)
-  int nsph_up = 0;  // spheres of the scene being uploaded (the device grid builders)
   // behind grid (Scene::ug_*), built at upload
   int ug_mode = -1;  // RT_HIP_BEHIND_GRID: -1 auto (scenes above kBvhAlwaysAbove spheres), 0 off, 1 on
   // RT_HIP_GRID_CLOSEST: 1 (default) = with the grid, closest hits walk it along the whole line instead of the
@@ -1995,31 +1971,12 @@ struct rt_ctx {
   // the BVH boxes it replaces)
   int ug_closest = 1;
   double ug_cells = 2.0;  // RT_HIP_GRID_CELLS: cells per listed sphere
-  bool ug_last = false;  // the most recent launch used it
-  double ug_build_ms = 0.0;
-  int bvh_min = 24, bvh_on = 1, bvh_groups = 2, bvh_leaf = 4;
+  int bvh_min = 24, bvh_on = 1, bvh_groups = 2;  // RT_HIP_BVH_MIN, RT_HIP_BVH, RT_HIP_BVH_GROUPS
   // RT_HIP_BVH_LEAF; 0 = 2, or 1 above kBvhAlwaysAbove spheres (rt_upload_scene)
   int bvh_leaf_opt = 0;
-  // -1 (auto): every group walks the BVH when the scene has more than
-  // kBvhAlwaysAbove spheres (a linear cull sweep is O(n) per group)
+  // RT_HIP_BVH_ALWAYS; -1 (auto): every group walks the BVH when the scene has
+  // more than kBvhAlwaysAbove spheres (a linear cull sweep is O(n) per group)
   int bvh_always = -1;
-  int n_cu = 256;
-  // Counters: two halves of one allocation, alternating by launch; d_counters
-  // is the half of the latest launch (what rt_render_stats reads).  A
-  // render_kernel launch zeroes the other half for the next launch, so the
-  // default path needs no separate memset (a fill kernel per frame).
-  unsigned long long *d_counters = nullptr;  // into ctr_base
-  DevBuf<unsigned long long> ctr_base;
-  bool ctr_clean[2] = {true, true};
-  bool zero_pending = false;  // the launch being enqueued zeroes the other half
-  PinnedBuf<unsigned long long> h_counters;
-  // In-stream HIP events around every render launch (a ring), so a caller can
-  // time a whole region of launches and read the per-launch durations after.
-  static constexpr int kRing = 256;
-  hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};
-  long long launches = 0, hist_begin = 0;
-  DevBuf<uint8_t> tmp;  // rt_render to host memory: the image on the device
-  int samples = 1;  // 4: the antialias mode (rt_set_antialias)
   int stack_mode = 4;  // RT_HIP_STACK: 4 merged reflection levels (default), 1 per-pixel global stack (one tile per wave)
   // RT_HIP_DEFER: kStackMerge defers rays of level >= kDeferLevel to render_deferred
   // (-1, default: in multi-frame launches only; 0 never; 1 always).  A one-frame
@@ -2029,29 +1986,9 @@ struct rt_ctx {
   // per frame without it)
   int defer = -1;
   bool defer_walk = true;  // RT_HIP_DEFER_WALK: deferred rays of a scene whose closest hits always walk the BVH use render_deferred_walk
-  int merge_q = 64;           // kStackMerge: the launch's LDS queue entries per wave (launch_render picks it)
-  int merge_q_max = 64;       // RT_HIP_MERGE_Q: longest queue tried (8, 16, 32 or 64)
+  int merge_q_max = 64;       // RT_HIP_MERGE_Q: longest LDS ray queue per wave tried (8, 16, 32 or 64; launch_render)
   int defer_level = kDeferLevel;  // RT_HIP_DEFER_LEVEL (>= 1)
   int defer_div = RT_DEFER_CAP_DIV;  // RT_HIP_DEFER_DIV (tuning build): queue room = launch pixels / defer_div
-  DevBuf<QRay> dq;            // its queue (and its slots' stacks), grow-only
-  // kStackMerge: the merged waves' stack homes (merge_tiles, home_acquire),
-  // twice as many as the render kernel can have resident, and their bitmap
-  // (one bit per home)
-  DevBuf<StackEnt> homes;
-  DevBuf<unsigned long long> home_bits;
-  const void *occ_kernel = nullptr;  // the occupancy of the last kernel asked (blocks per CU at occ_lds)
-  size_t occ_lds = 0;
-  int occ_blocks = 0;
-  // frames of the launch being enqueued (rt_render_frames_async; 1 otherwise) and their cameras
-  int nframes = 1;
-  const rt_camera *fcams = nullptr;
-  // rt_render_tiles: the requested tiles of the launch being enqueued, and the
-  // launch-order buffer of the blocks covering them
-  const rt_tile *req_tiles = nullptr;
-  int req_n = 0;
-  DevBuf<int> bperm;
-  PinnedBuf<int> h_bperm;
-  DevBuf<StackEnt> gstack;  // kStackGlobal: the per-pixel reflection stack, grow-only
   // RT_HIP_LDS_SCENE=1: stage scenes that fit (<= kLdsBudget) in LDS, 4-wave
   // workgroups.  Off by default: one-wave workgroups reading the scene through
   // L2 free each wave's slot as soon as its own tile is done (synth200:
@@ -2060,16 +1997,10 @@ struct rt_ctx {
   // Launch order of the tiles (rt_sched.h), rebuilt when the view or the
   // scene changes; RT_HIP_SCHED=0 dispatches in scanline order.
   int sched = 1;
-  unsigned long long scene_gen = 0;
-  SchedView perm_view{};
-  unsigned long long perm_gen = ~0ull;
-  DevBuf<int> perm;
-  PinnedBuf<int> h_perm;
-  long long perm_cls[kSchedClasses] = {};  // tiles per class of the cached order
   // kStackMerge: tiles of this class and above get a wave each (RT_HIP_SINGLE_CLASS
   // for every launch; kSchedClasses = none).  Default: every tile (class >= 0)
   // in one-frame launches, whose end is their slowest wave -- with no deferred
-  // kernel after them (defer, below): synth200 0.780 -> 0.372 ms, complex
+  // kernel after them (defer, above): synth200 0.780 -> 0.372 ms, complex
   // 0.652 -> 0.332 ms (profiles/r3r/ab_knobs.log); none in multi-frame
   // launches, where the other frames fill that tail and four tiles per wave
   // share their reflection rays' passes (class >= 1 there: 0.2285 -> 0.2364 ms
@@ -2093,11 +2024,144 @@ struct rt_ctx {
   // 2.49 ms per frame); synth200 keeps the adjacent order (0.1943 vs 0.1958
   // ms per frame at 32 frames, equal at 20; profiles/r3u/ab_xcd_frames.log)
   int xcd_frames = -1;
-  // rt_get_info: host-side builds made by the render calls
-  bool cg_last = false;
+};
+
+static Knobs read_knobs() {
+  Knobs k;
+  if (const char *e = std::getenv("RT_HIP_LDS_SCENE")) k.lds_scene = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_CAM_GRID")) k.cg_mode = std::max(0, std::min(2, std::atoi(e)));
+#ifdef RT_TUNING
+  if (const char *e = std::getenv("RT_HIP_BVH")) k.bvh_on = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_BVH_MIN")) k.bvh_min = std::atoi(e);
+  if (const char *e = std::getenv("RT_HIP_BVH_ALWAYS")) k.bvh_always = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_BVH_GROUPS")) k.bvh_groups = std::max(1, std::atoi(e));
+  if (const char *e = std::getenv("RT_HIP_SHADOW_GRID")) k.lg_on = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_SCHED")) k.sched = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_STACK")) k.stack_mode = std::atoi(e) == kStackGlobal ? kStackGlobal : kStackMerge;
+  if (const char *e = std::getenv("RT_HIP_BVH_ORDERED")) k.bvh_ordered = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_BVH4")) k.bvh_wide = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_BVH_LEAF")) k.bvh_leaf_opt = std::max(1, std::min(15, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_DEFER")) k.defer = std::atoi(e) != 0 ? 1 : 0;
+  if (const char *e = std::getenv("RT_HIP_DEFER_WALK")) k.defer_walk = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_DEFER_LEVEL")) k.defer_level = std::max(1, std::min(RT_MAX_DEPTH, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_MERGE_Q")) k.merge_q_max = std::max(8, std::min(64, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_SHADOW_GRID_N")) k.lg_n_opt = std::max(1, std::min(1024, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_CAM_GRID_N")) k.cg_n_opt = std::max(1, std::min(1024, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_CAM_GRID_BUDGET")) k.cg_budget_opt = std::max(0LL, std::atoll(e));
+  if (const char *e = std::getenv("RT_HIP_CAM_GRID_MAXP")) k.cg_maxp_opt = std::max(1LL, std::atoll(e));
+  if (const char *e = std::getenv("RT_HIP_SPHERE_GRID")) k.sg_mode = std::max(-1, std::min(1, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_SPHERE_GRID_N")) k.sg_n_opt = std::max(1, std::min(256, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_BEHIND_GRID")) k.ug_mode = std::max(-1, std::min(1, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_GRID_CLOSEST")) k.ug_closest = std::atoi(e) != 0 ? 1 : 0;
+  if (const char *e = std::getenv("RT_HIP_XCD_FRAMES")) k.xcd_frames = std::max(-1, std::min(1, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_TAIL")) k.tail = std::atoi(e) != 0;
+  if (const char *e = std::getenv("RT_HIP_TAIL_WAVES")) k.tail_waves = std::max(1, std::min(64, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_WIDE")) k.wide_mode = std::max(0, std::min(3, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_DEFER_DIV")) k.defer_div = std::max(1, std::min(1024, std::atoi(e)));
+  if (const char *e = std::getenv("RT_HIP_GRID_CELLS")) k.ug_cells = std::max(0.05, std::min(64.0, std::atof(e)));
+  if (const char *e = std::getenv("RT_HIP_SINGLE_CLASS"))
+    k.single_class = std::max(0, std::min(kSchedClasses, std::atoi(e)));
+#endif
+  return k;
+}
+
+// Camera grids (rt_device.h CgArgs), built on the device per camera position
+// of a launch (cg_bin_kernel / cg_sort_kernel) and kept while the positions
+// and the scene stay the same.
+struct CgTables {  // the cube map's patch tables of one N on the device
+  int N = 0, NT = 0, NB = 0;
+  DevBuf<CubePatch> faces, blocks, tiles;
+  DevBuf<double> cell;
+};
+struct CamGrids {
+  DevBuf<int32_t> count;
+  DevBuf<int2> ent, pairs;
+  DevBuf<CgDisk> disks;
+  DevBuf<unsigned> npairs;
+  size_t bytes() const { return count.bytes() + ent.bytes() + disks.bytes() + pairs.bytes() + npairs.bytes(); }
+  int n = 0, ngrid = 0;
+  std::vector<double> pos;   // the grids' points (3 per grid)
+  std::vector<double> seen;  // the previous launch's camera positions
+  unsigned long long seen_gen = ~0ull;
+  unsigned long long gen = ~0ull;  // scene_gen they were built for
+  CgTables tab[2];
+  int tab_next = 0;
+};
+
+// The cached launch order of the tiles (tile_perm) and the view it was built for.
+struct TileOrder {
+  SchedView view{};
+  unsigned long long gen = ~0ull;
+  DevBuf<int> perm;
+  PinnedBuf<int> h_perm;
+  long long cls[kSchedClasses] = {};  // tiles per class of the cached order
+};
+
+// Counters: two halves of one allocation, alternating by launch; cur is the
+// half of the latest launch (what rt_render_stats reads).  A render_kernel
+// launch zeroes the other half for the next launch, so the default path needs
+// no separate memset (a fill kernel per frame).
+struct Counters {
+  unsigned long long *cur = nullptr;  // into base
+  DevBuf<unsigned long long> base;
+  bool clean[2] = {true, true};
+  PinnedBuf<unsigned long long> host;
+};
+
+// In-stream HIP events around every render launch (a ring), so a caller can
+// time a whole region of launches and read the per-launch durations after.
+struct LaunchTiming {
+  static constexpr int kRing = 256;
+  hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};
+  long long launches = 0, hist_begin = 0;
+  int slot() const { return (int)(launches % kRing); }  // of the launch being enqueued
+};
+
+// The occupancy of the last kernel asked (blocks per CU at lds).
+struct OccCache {
+  const void *kernel = nullptr;
+  size_t lds = 0;
+  int blocks = 0;
+};
+
+// What rt_get_info reports of the builds made by uploads and render calls.
+// None of it is reset by an upload: each figure is that of its latest build.
+struct BuildInfo {
+  bool cg_last = false, ug_last = false;  // the most recent launch used camera grids / the behind grid
   int cg_last_n = 0;
   unsigned long long cg_builds = 0, perm_builds = 0;
-  double cg_build_ms = 0.0, perm_build_ms = 0.0, upload_ms = 0.0;
+  double cg_build_ms = 0.0, perm_build_ms = 0.0, upload_ms = 0.0, sg_build_ms = 0.0, ug_build_ms = 0.0;
+  double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds
+};
+
+struct rt_ctx {
+  explicit rt_ctx(int dev, const Knobs &k) : device(dev), knobs(k) {}
+  const int device;
+  int n_cu = 256;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  hipEvent_t switch_ev = nullptr;  // rt_set_stream: orders the new stream after the old one
+  const Knobs knobs;
+  // the caller's settings
+  bool cull = true;  // rt_set_culling
+  int samples = 1;   // 4: the antialias mode (rt_set_antialias)
+  Scene scene;
+  unsigned long long scene_gen = 0;  // counts the uploads: what the caches below were built for
+  CamGrids cg;
+  TileOrder order;
+  Counters ctr;
+  LaunchTiming timing;
+  OccCache occ;
+  BuildInfo info;
+  // grow-only scratch of the launches
+  DevBuf<uint8_t> tmp;      // rt_render to host memory: the image on the device
+  DevBuf<QRay> dq;          // kStackMerge: the deferred queue (and its slots' stacks)
+  // kStackMerge: the merged waves' stack homes (merge_tiles, home_acquire), twice as many
+  // as the render kernel can have resident, and their bitmap (one bit per home)
+  DevBuf<StackEnt> homes;
+  DevBuf<unsigned long long> home_bits;
+  DevBuf<int> bperm;        // rt_render_tiles: the launch-order buffer of the blocks covering the tiles
+  PinnedBuf<int> h_bperm;
+  DevBuf<StackEnt> gstack;  // kStackGlobal: the per-pixel reflection stack
   std::string err;
 };
 
@@ -2105,9 +2169,6 @@ namespace {
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
-}  // namespace
-
-namespace {
 
 int fail(rt_ctx *c, hipError_t e, const char *what) {
   if (c) c->err = std::string(what) + ": " + hipGetErrorString(e);
@@ -2120,9 +2181,31 @@ int fail(rt_ctx *c, hipError_t e, const char *what) {
     if (e_ != hipSuccess) return fail(ctx, e_, #call); \
   } while (0)
 
+// One render launch as its entry point asked for it; validate checks it and
+// enqueue passes it down: nothing of a launch's arguments is kept in rt_ctx.
+struct LaunchReq {
+  const rt_camera *cams;  // nframes of them (more than one: rt_render_frames_async)
+  int nframes;
+  int W, H, depth;
+  Rows rows;
+  OutDesc od;
+  const rt_tile *tiles = nullptr;  // rt_render_tiles: only the blocks covering these are rendered
+  int ntiles = 0;
+};
+
 void free_scene(rt_ctx *c) {
   c->scene = Scene{};
-  c->cg_gen = ~0ull;
+  c->cg.gen = ~0ull;
+}
+
+// The diameter of the scene's bounds extended by the point p.
+double extent_with(const Scene &sc, const double *p) {
+  double d2 = 0.0;
+  for (int k = 0; k < 3; k++) {
+    const double l = std::min(sc.lo[k], p[k]), h = std::max(sc.hi[k], p[k]);
+    d2 += (h - l) * (h - l);
+  }
+  return std::sqrt(d2);
 }
 
 // BVH arguments for one render: the scene extent includes the camera (the
@@ -2135,35 +2218,28 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
   b.pf = sc.pf.get();
   b.n2 = sc.bvh2.get();
   b.root_ref = sc.bvh2_root;
-  b.nnodes = (c->bvh_on && c->cull) ? sc.bvh_nodes : 0;
+  b.nnodes = (c->knobs.bvh_on && c->cull) ? sc.bvh_nodes : 0;
   b.nn2 = sc.bvh2_nodes;
   b.nn4 = sc.bvh4_nodes;
   b.nprims = sc.bvh_prims;
   b.n4 = sc.bvh4.get();
   b.root4 = sc.bvh4_root;
-  b.wide = (c->bvh_wide && b.n4 && sc.bvh4_stack <= kOrderedStack) ? 1 : 0;
-  b.ordered = (c->bvh_ordered && b.nnodes > 0 && (b.wide || (b.n2 && sc.bvh_depth <= kOrderedStack))) ? 1 : 0;
+  b.wide = (c->knobs.bvh_wide && b.n4 && sc.bvh4_stack <= kOrderedStack) ? 1 : 0;
+  b.ordered = (c->knobs.bvh_ordered && b.nnodes > 0 && (b.wide || (b.n2 && sc.bvh_depth <= kOrderedStack))) ? 1 : 0;
   if (!b.ordered) b.wide = 0;
   b.odepth = std::max(1, b.wide ? sc.bvh4_stack : sc.bvh_depth);
   b.ostk = nullptr;  // set in the kernel (LDS), or found at ostk_off
   b.ostk_off = -1;
-  b.c0x = sc.c0[0];
-  b.c0y = sc.c0[1];
-  b.c0z = sc.c0[2];
+  b.c0x = sc.c0[0], b.c0y = sc.c0[1], b.c0z = sc.c0[2];
   const double cp[3] = {cam.px, cam.py, cam.pz};
-  double d2 = 0.0;
-  for (int k = 0; k < 3; k++) {
-    const double l = std::min(sc.lo[k], cp[k]), h = std::max(sc.hi[k], cp[k]);
-    d2 += (h - l) * (h - l);
-  }
-  b.diam = std::sqrt(d2) + 0.01;  // + the 0.001 origin offsets of secondary rays
+  b.diam = extent_with(sc, cp) + 0.01;  // + the 0.001 origin offsets of secondary rays
   const double m = 1e-6 * (b.diam + sc.rmax);
   b.margin = std::isfinite(m) ? (float)(m * (1.0 + 1e-6)) : INFINITY;
   b.pmargin = 4.0f * b.margin;
   if (!std::isfinite(b.diam)) b.diam = INFINITY;
-  b.min_cands = c->bvh_min;
-  b.always = c->bvh_always >= 0 ? c->bvh_always : (sc.nsph > kBvhAlwaysAbove ? 1 : 0);
-  b.max_groups = c->bvh_groups;
+  b.min_cands = c->knobs.bvh_min;
+  b.always = c->knobs.bvh_always >= 0 ? c->knobs.bvh_always : (sc.nsph > kBvhAlwaysAbove ? 1 : 0);
+  b.max_groups = c->knobs.bvh_groups;
   // the behind grid, when its listing margin covers this view's prefilter
   // margin plus the DDA's error bound (rt_device.h behind_cells); the ordered
   // walks then skip boxes wholly behind the origin
@@ -2173,7 +2249,7 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
       (double)b.pmargin + 1e-4 * (double)sc.ug_extent <= (double)sc.ug_reg_margin) {
     b.ug = sc.ug;
     b.ug.on = 1;
-    b.ug.closest = c->ug_closest;
+    b.ug.closest = c->knobs.ug_closest;
     b.tf_min = 0.0f;
     // no closest hit walks the BVH then (the shadow queries use the light
     // grids or the stackless walk): no LDS stacks for the ordered walk, so
@@ -2185,14 +2261,10 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
 
 LgArgs lg_args(const rt_ctx *c) {
   LgArgs g{};
-  g.start = c->scene.lg_start.get();
-  g.ids = c->scene.lg_ids.get();
-  g.N = c->lg_n;
-  g.on = (c->lg_on && c->cull && g.start) ? 1 : 0;
-  g.max_off = c->lg_max_off;
-  g.off_free = c->lg_off_free ? 1 : 0;
-  g.nstart = c->scene.lg_nstart;
-  g.nids = c->scene.lg_nids;
+  g.start = c->scene.lg_start.get(), g.ids = c->scene.lg_ids.get(), g.N = c->scene.lg_n;
+  g.on = (c->knobs.lg_on && c->cull && g.start) ? 1 : 0;
+  g.max_off = c->scene.lg_max_off, g.off_free = c->scene.lg_off_free ? 1 : 0;
+  g.nstart = c->scene.lg_nstart, g.nids = c->scene.lg_nids;
   return g;
 }
 
@@ -2203,20 +2275,20 @@ LgArgs lg_args(const rt_ctx *c) {
 // a grid per frame (a quarter of the cells to build)
 constexpr int kCgNStatic = 256, kCgNMoving = 128;
 
-int upload_tables(rt_ctx *c, int N, rt_ctx::CgTables &t);
+int upload_tables(rt_ctx *c, int N, CgTables &t);
 
 // The device patch tables of the cube map with N cells per face edge (two
 // kept; replacing one waits for the launches in flight).
-int cg_tables(rt_ctx *c, int N, const rt_ctx::CgTables *&out) {
-  for (const auto &t : c->cg_tab)
+int cg_tables(rt_ctx *c, int N, const CgTables *&out) {
+  for (const auto &t : c->cg.tab)
     if (t.N == N) {
       out = &t;
       return RT_OK;
     }
-  rt_ctx::CgTables &t = c->cg_tab[c->cg_tab_next];
-  c->cg_tab_next ^= 1;
+  CgTables &t = c->cg.tab[c->cg.tab_next];
+  c->cg.tab_next ^= 1;
   RT_TRY(c, hipStreamSynchronize(c->stream));
-  t = rt_ctx::CgTables{};
+  t = CgTables{};
   const int rc = upload_tables(c, N, t);
   if (rc != RT_OK) return rc;
   out = &t;
@@ -2224,7 +2296,7 @@ int cg_tables(rt_ctx *c, int N, const rt_ctx::CgTables *&out) {
 }
 
 // The cube map's patch tables for N cells per face edge, on the device.
-int upload_tables(rt_ctx *c, int N, rt_ctx::CgTables &t) {
+int upload_tables(rt_ctx *c, int N, CgTables &t) {
   std::vector<CubePatch> faces, blocks, tiles;
   std::vector<double> cell;
   int NT = 0, NB = 0;
@@ -2278,7 +2350,7 @@ struct CgPlan {
   int N = 0, ngrid = 0, maxp = 0;
   long long nblocks = 0;
   std::vector<double> pos;
-  const rt_ctx::CgTables *tab = nullptr;
+  const CgTables *tab = nullptr;
 };
 
 // The camera grids of this launch (plan.use = false: the launch sweeps as
@@ -2287,29 +2359,29 @@ struct CgPlan {
 // -- policy, tables, buffers (which may wait for the stream) -- runs before
 // the launch's start event; cam_grid_enqueue puts the device passes on the
 // stream ahead of the render kernel.
-int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
+int cam_grid_prepare(rt_ctx *c, const LaunchReq &q, CgPlan &p) {
   p = CgPlan{};
-  const int nsph = c->scene.nsph;
-  if (c->cg_mode == 0 || !c->cull || nsph == 0) return RT_OK;
-  std::vector<double> pos{cam.px, cam.py, cam.pz};
+  const int nsph = c->scene.nsph, nf = q.nframes;
+  if (c->knobs.cg_mode == 0 || !c->cull || nsph == 0) return RT_OK;
+  std::vector<double> pos(q.cams[0].position, q.cams[0].position + 3);
   bool same = true;
-  for (int f = 1; f < nf; f++) same = same && std::memcmp(c->fcams[f].position, pos.data(), 3 * sizeof(double)) == 0;
+  for (int f = 1; f < nf; f++) same = same && std::memcmp(q.cams[f].position, pos.data(), 3 * sizeof(double)) == 0;
   const int ngrid = same ? 1 : nf;
-  for (int f = 1; f < ngrid; f++) pos.insert(pos.end(), c->fcams[f].position, c->fcams[f].position + 3);
-  const int N = c->cg_n_opt ? c->cg_n_opt : (same ? kCgNStatic : kCgNMoving);
+  for (int f = 1; f < ngrid; f++) pos.insert(pos.end(), q.cams[f].position, q.cams[f].position + 3);
+  const int N = c->knobs.cg_n_opt ? c->knobs.cg_n_opt : (same ? kCgNStatic : kCgNMoving);
   const size_t cells = 6 * (size_t)N * N;
   if (ngrid * cells * kCgSlots >= (size_t(1) << 31)) return RT_OK;  // the scan's 32-bit slot index: no grid
-  const bool cached = c->cg_gen == c->scene_gen && c->cg_n == N && c->cg_ngrid == ngrid && c->cg_pos == pos;
-  if (!cached && nf == 1 && c->cg_mode == 1 && !(c->cg_seen_gen == c->scene_gen && c->cg_seen == pos)) {
+  const bool cached = c->cg.gen == c->scene_gen && c->cg.n == N && c->cg.ngrid == ngrid && c->cg.pos == pos;
+  if (!cached && nf == 1 && c->knobs.cg_mode == 1 && !(c->cg.seen_gen == c->scene_gen && c->cg.seen == pos)) {
     // one frame from a position the previous launch did not use: the build
     // (~0.05 ms) costs more than the grid saves that frame (profiles/r4j/);
     // the position's next launch gets the grid
-    c->cg_seen = pos;
-    c->cg_seen_gen = c->scene_gen;
+    c->cg.seen = pos;
+    c->cg.seen_gen = c->scene_gen;
     return RT_OK;
   }
-  c->cg_seen = pos;
-  c->cg_seen_gen = c->scene_gen;
+  c->cg.seen = pos;
+  c->cg.seen_gen = c->scene_gen;
   if (cached) {
     p.use = true;
     p.N = N;
@@ -2317,8 +2389,8 @@ int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
     return RT_OK;
   }
   // from here the buffers change: the cached grids are gone whatever happens
-  c->cg_gen = ~0ull;
-  const rt_ctx::CgTables *tab = nullptr;
+  c->cg.gen = ~0ull;
+  const CgTables *tab = nullptr;
   int rc = cg_tables(c, N, tab);
   if (rc != RT_OK) return rc;
   const long long nblocks = 6LL * tab->NB * tab->NB;
@@ -2329,7 +2401,7 @@ int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
   const unsigned long long cap32 = ((1ull << 32) - 1) / (4ull * (unsigned long long)ngrid);
   const unsigned long long budget = std::max<unsigned long long>(1, kCgPairBytes / sizeof(int2) / ngrid);
   int maxp = (int)std::min({worst, cap32, budget, (unsigned long long)INT32_MAX});
-  if (c->cg_maxp_opt >= 0) maxp = (int)std::max<long long>(1, std::min<long long>(maxp, c->cg_maxp_opt));
+  if (c->knobs.cg_maxp_opt >= 0) maxp = (int)std::max<long long>(1, std::min<long long>(maxp, c->knobs.cg_maxp_opt));
   const size_t b_count = ngrid * cells * sizeof(int32_t), b_ent = ngrid * cells * kCgSlots * sizeof(int2),
                b_np = (size_t)ngrid * kCgCntStride * sizeof(unsigned),
                b_disks = 2 * (size_t)nsph * ngrid * sizeof(CgDisk), b_pairs = (size_t)ngrid * maxp * sizeof(int2);
@@ -2340,11 +2412,11 @@ int cam_grid_prepare(rt_ctx *c, const Cam &cam, int nf, CgPlan &p) {
     free_b = 0;
   }
   // what the grids hold now counts as available: growing frees it first
-  const size_t held = c->cg_bytes();
-  const size_t limit = c->cg_budget_opt >= 0 ? (size_t)c->cg_budget_opt : kCgBudgetBytes;
+  const size_t held = c->cg.bytes();
+  const size_t limit = c->knobs.cg_budget_opt >= 0 ? (size_t)c->knobs.cg_budget_opt : kCgBudgetBytes;
   if (total > limit || total > (free_b + held) / 2) return RT_OK;
-  if (!grow_soft(c, c->cg_count, b_count) || !grow_soft(c, c->cg_ent, b_ent) || !grow_soft(c, c->cg_npairs, b_np) ||
-      !grow_soft(c, c->cg_disks, b_disks) || !grow_soft(c, c->cg_pairs, b_pairs))
+  if (!grow_soft(c, c->cg.count, b_count) || !grow_soft(c, c->cg.ent, b_ent) || !grow_soft(c, c->cg.npairs, b_np) ||
+      !grow_soft(c, c->cg.disks, b_disks) || !grow_soft(c, c->cg.pairs, b_pairs))
     return RT_OK;  // no memory for the grid: this launch sweeps
   p.use = p.build = true;
   p.N = N;
@@ -2362,37 +2434,19 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
   const size_t cells = 6 * (size_t)p.N * p.N;
   if (p.build) {
     const auto t0 = std::chrono::steady_clock::now();
-    const rt_ctx::CgTables *tab = p.tab;
+    const CgTables *tab = p.tab;
     const int ngrid = p.ngrid;
     CgBuild b{};
-    b.geo = c->scene.geo.get();
-    b.rad = c->scene.rad.get();
-    b.faces = tab->faces.get();
-    b.blocks = tab->blocks.get();
-    b.tiles = tab->tiles.get();
-    b.cell_cbsb = tab->cell.get();
-    b.count = c->cg_count.get();
-    b.ent = c->cg_ent.get();
-    b.disks = c->cg_disks.get();
-    b.pairs = c->cg_pairs.get();
-    b.npairs = c->cg_npairs.get();
-    b.maxp = p.maxp;
-    b.n = c->scene.nsph;
-    b.N = p.N;
-    b.NT = tab->NT;
-    b.NB = tab->NB;
-    b.K = kCgSlots;
-    b.ngrid = ngrid;
+    b.geo = c->scene.geo.get(), b.rad = c->scene.rad.get();
+    b.faces = tab->faces.get(), b.blocks = tab->blocks.get(), b.tiles = tab->tiles.get(), b.cell_cbsb = tab->cell.get();
+    b.count = c->cg.count.get(), b.ent = c->cg.ent.get(), b.disks = c->cg.disks.get();
+    b.pairs = c->cg.pairs.get(), b.npairs = c->cg.npairs.get(), b.maxp = p.maxp;
+    b.n = c->scene.nsph, b.N = p.N, b.NT = tab->NT, b.NB = tab->NB, b.K = kCgSlots, b.ngrid = ngrid;
     for (int g = 0; g < ngrid; g++) {
       b.px[g] = p.pos[3 * g];
       b.py[g] = p.pos[3 * g + 1];
       b.pz[g] = p.pos[3 * g + 2];
-      double d2 = 0.0;  // the scene's extent with the point (the grown radius' margin)
-      for (int k = 0; k < 3; k++) {
-        const double l = std::min(c->scene.lo[k], p.pos[3 * g + k]), h = std::max(c->scene.hi[k], p.pos[3 * g + k]);
-        d2 += (h - l) * (h - l);
-      }
-      b.diam[g] = std::sqrt(d2);
+      b.diam[g] = extent_with(c->scene, &p.pos[3 * (size_t)g]);  // (the grown radius' margin)
     }
     RT_TRY(c, hipMemsetAsync(b.count, 0, ngrid * cells * sizeof(int32_t), c->stream));
     RT_TRY(c, hipMemsetAsync(b.npairs, 0, ngrid * kCgCntStride * sizeof(unsigned), c->stream));
@@ -2403,14 +2457,14 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
     hipLaunchKernelGGL(cg_sort_kernel, dim3((unsigned)((ngrid * cells + 255) / 256)), dim3(256), 0, c->stream, b);
     RT_TRY(c, hipGetLastError());
     // the grids are valid for later launches only once their passes are on the stream
-    c->cg_gen = c->scene_gen;
-    c->cg_n = p.N;
-    c->cg_ngrid = ngrid;
-    c->cg_pos = p.pos;
-    c->cg_builds++;
-    c->cg_build_ms += ms_since(t0);
+    c->cg.gen = c->scene_gen;
+    c->cg.n = p.N;
+    c->cg.ngrid = ngrid;
+    c->cg.pos = p.pos;
+    c->info.cg_builds++;
+    c->info.cg_build_ms += ms_since(t0);
   }
-  out = CgArgs{c->cg_count.get(), c->cg_ent.get(), p.N, 1, p.ngrid > 1 ? 1 : 0, p.ngrid};
+  out = CgArgs{c->cg.count.get(), c->cg.ent.get(), p.N, 1, p.ngrid > 1 ? 1 : 0, p.ngrid};
   return RT_OK;
 }
 
@@ -2450,7 +2504,8 @@ int device_scan(rt_ctx *c, const int *x, long long n, int *y, long long &total) 
   return RT_OK;
 }
 
-// Point grids on the device (pg_*_kernel passes) for the grids `pts`, each
+// Point grids on the device (pg_*_kernel passes) over the n spheres of
+// scene.geo / scene.rad (uploaded; scene.nsph is set later) for the grids `pts`, each
 // with N cells per cube-map face edge: per grid ok (sphere grids: refused past
 // max_global global spheres or dropped pairs; light grids: never), the CSR
 // offsets of the ng x row lists (device, ng * row + 1 ints, held by `keep`)
@@ -2465,15 +2520,15 @@ struct PgMode {
   int near = 0;
 };
 template <class E>  // the entries: int2 for sphere grids, int32_t for light grids (md.globlist)
-int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<unsigned char> &allglob, double diam,
-                int N, const PgMode &md, DevScratch &keep, int *&d_off, std::vector<unsigned char> &ok,
+int point_grids(rt_ctx *c, int n, const std::vector<GridPt> &pts, const std::vector<unsigned char> &allglob,
+                double diam, int N, const PgMode &md, DevScratch &keep, int *&d_off, std::vector<unsigned char> &ok,
                 long long &total, DevBuf<E> &out) {
-  const int n = c->nsph_up, ng = (int)pts.size();
+  const int ng = (int)pts.size();
   const long long cells = 6LL * N * N, row = cells + (md.globlist ? 1 : 0);
   out.reset();
   total = 0;
   ok.assign((size_t)ng, 0);
-  rt_ctx::CgTables tab;
+  CgTables tab;
   int rc = upload_tables(c, N, tab);
   if (rc != RT_OK) return rc;
   const long long nblocks = 6LL * tab.NB * tab.NB;
@@ -2507,27 +2562,12 @@ int point_grids(rt_ctx *c, const std::vector<GridPt> &pts, const std::vector<uns
   RT_TRY(c, hipMemcpy(d_ag, allglob.data(), (size_t)ng, hipMemcpyHostToDevice));
   RT_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)(ng * row), c->stream));
   SgBuild b{};
-  b.geo = c->scene.geo.get();
-  b.rad = c->scene.rad.get();
-  b.faces = tab.faces.get();
-  b.blocks = tab.blocks.get();
-  b.tiles = tab.tiles.get();
-  b.cell_cbsb = tab.cell.get();
-  b.disks = d_disks;
-  b.pairs = d_pairs;
-  b.npairs = d_np;
-  b.nglob = d_np + kSgCntStride * (size_t)batch;
-  b.woff = d_woff;
-  b.off = d_off;
-  b.n = n;
-  b.N = N;
-  b.NT = tab.NT;
-  b.NB = tab.NB;
-  b.maxp = (int)maxp;
-  b.row = (int)row;
-  b.sides = md.sides;
-  b.globlist = md.globlist;
-  b.diam = diam;
+  b.geo = c->scene.geo.get(), b.rad = c->scene.rad.get();
+  b.faces = tab.faces.get(), b.blocks = tab.blocks.get(), b.tiles = tab.tiles.get(), b.cell_cbsb = tab.cell.get();
+  b.disks = d_disks, b.pairs = d_pairs, b.npairs = d_np, b.nglob = d_np + kSgCntStride * (size_t)batch;
+  b.woff = d_woff, b.off = d_off;
+  b.n = n, b.N = N, b.NT = tab.NT, b.NB = tab.NB, b.maxp = (int)maxp, b.row = (int)row;
+  b.sides = md.sides, b.globlist = md.globlist, b.diam = diam;
   std::vector<std::vector<unsigned>> woffs;
   // one batch of grids: disks and pairs (pass 1) -- and, counting, the
   // grids' refusals and work offsets -- then the bin pass
@@ -2608,7 +2648,7 @@ int sphere_grids(rt_ctx *c) {
   const int n = (int)src.size();
   const double diam = scn.sg_diam;
   scn.sg_pending = false;
-  if (c->sg_mode == 0 || (c->sg_mode < 0 && n > kSgMaxSpheres) || n == 0 || !std::isfinite(diam)) return RT_OK;
+  if (c->knobs.sg_mode == 0 || (c->knobs.sg_mode < 0 && n > kSgMaxSpheres) || n == 0 || !std::isfinite(diam)) return RT_OK;
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<double> rho((size_t)n, -1.0);
   std::vector<int> gidx((size_t)n, -1);
@@ -2624,7 +2664,7 @@ int sphere_grids(rt_ctx *c) {
       pts.push_back(GridPt{sp.center[0], sp.center[1], sp.center[2], rho[(size_t)i]});
     }
   }
-  const int N = c->sg_n_opt ? c->sg_n_opt : (n <= kSgFineSpheres ? kSgNFine : kSgN);
+  const int N = c->knobs.sg_n_opt ? c->knobs.sg_n_opt : (n <= kSgFineSpheres ? kSgNFine : kSgN);
   // the device indexes grid key's starts at key * (6 N^2 + 1) in 32 bits, and
   // every sphere has its row of starts: refuse grids that would overflow it
   // or hold more than 1 GiB of starts
@@ -2635,7 +2675,7 @@ int sphere_grids(rt_ctx *c) {
   scn.sg_grids = 0;
   scn.sg_entries = 0;
   if (ng == 0 || (long long)ng * cells >= INT32_MAX) {  // (32-bit CSR offsets)
-    c->sg_build_ms = ms_since(t0);
+    c->info.sg_build_ms = ms_since(t0);
     return RT_OK;
   }
   // built in buffers of this call, handed to the scene when complete: a
@@ -2647,13 +2687,13 @@ int sphere_grids(rt_ctx *c) {
   DevBuf<int2> ent;
   DevBuf<int32_t> start;
   DevBuf<double> d_rho2;
-  int rc = point_grids(c, pts, std::vector<unsigned char>((size_t)ng, 0), diam, N,
+  int rc = point_grids(c, n, pts, std::vector<unsigned char>((size_t)ng, 0), diam, N,
                        PgMode{2, 0, kSgMaxGlobal, kSgMaxEntries}, keep, d_off, ok, total, ent);
   if (rc != RT_OK) return rc;
   int grids = 0;
   for (int j = 0; j < ng; j++) grids += ok[(size_t)j];
   if (!ent.get() || grids == 0) {  // as build_sphere_grids past max_entries: no grids
-    c->sg_build_ms = ms_since(t0);
+    c->info.sg_build_ms = ms_since(t0);
     return RT_OK;
   }
   DevScratch sc;
@@ -2683,7 +2723,7 @@ int sphere_grids(rt_ctx *c) {
   scn.sg_ok = true;
   scn.sg_grids = grids;
   scn.sg_entries = (size_t)total;
-  c->sg_build_ms = ms_since(t0);
+  c->info.sg_build_ms = ms_since(t0);
   return RT_OK;
 }
 
@@ -2781,11 +2821,11 @@ void stage_scene(const rt_scene *s, int bvh_leaf, bool want_ug, double ug_cells,
 // fit 32-bit offsets.
 int light_grids(rt_ctx *c, const rt_scene *s, const StagedScene &st) {
   const auto t0 = std::chrono::steady_clock::now();
-  const int n = s->num_spheres, nl = s->num_lights, N = c->lg_n;
+  const int n = s->num_spheres, nl = s->num_lights, N = c->scene.lg_n;
   const double diam = st.diam;
   Scene &scn = c->scene;
   const long long cells = 6LL * N * N;
-  c->lg_max_off = std::isfinite(diam) ? 1e-7 * diam : 0.0;
+  c->scene.lg_max_off = std::isfinite(diam) ? 1e-7 * diam : 0.0;
   {
     // every hit point lies on a finite sphere, inside the scene box up to
     // rounding, and every light inside it: with B the box's largest |coordinate|
@@ -2793,7 +2833,7 @@ int light_grids(rt_ctx *c, const rt_scene *s, const StagedScene &st) {
     // 2^-41 (1.01 B + 0.01) (shadow_cells), so the per-ray check can go
     double B = 0.0;
     for (int k = 0; k < 3; k++) B = std::max(B, std::max(std::fabs(st.lo[k]), std::fabs(st.hi[k])));
-    c->lg_off_free = std::isfinite(B) && c->lg_max_off > 0.0 && 0x1p-41 * (1.01 * B + 0.01) <= c->lg_max_off;
+    c->scene.lg_off_free = std::isfinite(B) && c->scene.lg_max_off > 0.0 && 0x1p-41 * (1.01 * B + 0.01) <= c->scene.lg_max_off;
   }
   const double dm = std::isfinite(diam) ? diam : 0.0;
   std::vector<GridPt> pts((size_t)nl);
@@ -2809,8 +2849,8 @@ int light_grids(rt_ctx *c, const rt_scene *s, const StagedScene &st) {
     DevScratch keep;
     int *d_off = nullptr;
     std::vector<unsigned char> ok;
-    int rc = point_grids(c, pts, allglob, dm, N, PgMode{1, 1, INT32_MAX, (size_t)INT32_MAX, 1}, keep, d_off,
-                         ok, total, scn.lg_ids);
+    int rc = point_grids(c, n, pts, allglob, dm, N, PgMode{1, 1, INT32_MAX, (size_t)INT32_MAX, 1}, keep, d_off, ok,
+                         total, scn.lg_ids);
     if (rc != RT_OK) return rc;
     if (scn.lg_ids.get()) {
       const long long nstart = (long long)nl * (cells + 2);
@@ -2840,7 +2880,7 @@ int light_grids(rt_ctx *c, const rt_scene *s, const StagedScene &st) {
     RT_TRY(c, scn.lg_start.upload(lg_start, 1));
     RT_TRY(c, scn.lg_ids.upload(lg_ids, 1));
   }
-  c->lg_build_ms = ms_since(t0);
+  c->info.lg_build_ms = ms_since(t0);
   return RT_OK;
 }
 
@@ -2853,15 +2893,16 @@ Cam to_cam(const rt_camera &cm) {
 // The tile launch order for this view (rt_sched.h), on the device; rebuilt
 // only when the camera, the image/shard geometry, the tile size or the scene
 // changed since the last build.
-int tile_perm(rt_ctx *c, const Cam &cam, int W, int H, const Rows &rows, const OutDesc &od, int tw, int th,
-              long long ntiles, const int *&out) {
+int tile_perm(rt_ctx *c, const LaunchReq &q, const Cam &cam, int tw, int th, long long ntiles, const int *&out) {
+  const Rows &rows = q.rows;
+  const OutDesc &od = q.od;
   SchedView v{};
   v.px = cam.px, v.py = cam.py, v.pz = cam.pz, v.fx = cam.fx, v.fy = cam.fy, v.fz = cam.fz;
   v.rx = cam.rx, v.ry = cam.ry, v.rz = cam.rz, v.ux = cam.ux, v.uy = cam.uy, v.uz = cam.uz, v.scale = cam.scale;
-  v.W = W, v.H = H, v.band = rows.band, v.first = rows.first, v.stride = rows.stride, v.count = rows.count;
+  v.W = q.W, v.H = q.H, v.band = rows.band, v.first = rows.first, v.stride = rows.stride, v.count = rows.count;
   v.x0 = od.x0, v.xw = od.xw, v.tw = tw, v.th = th;
-  if (c->perm_gen == c->scene_gen && std::memcmp(&v, &c->perm_view, sizeof v) == 0 && c->perm.get()) {
-    out = c->perm.get();
+  if (c->order.gen == c->scene_gen && std::memcmp(&v, &c->order.view, sizeof v) == 0 && c->order.perm.get()) {
+    out = c->order.perm.get();
     return RT_OK;
   }
   const auto t0 = std::chrono::steady_clock::now();
@@ -2871,26 +2912,26 @@ int tile_perm(rt_ctx *c, const Cam &cam, int W, int H, const Rows &rows, const O
   if ((long long)perm.size() != ntiles) return RT_ERR_INVALID_ARG;
   const size_t bytes = perm.size() * sizeof(int);
   RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous order may still be in flight from h_perm
-  if (c->perm.bytes() < bytes || c->h_perm.bytes() < bytes) {  // grow-only, the pair together
-    c->perm_gen = ~0ull;
-    RT_TRY(c, c->perm.alloc(bytes));
-    RT_TRY(c, c->h_perm.alloc(bytes));
+  if (c->order.perm.bytes() < bytes || c->order.h_perm.bytes() < bytes) {  // grow-only, the pair together
+    c->order.gen = ~0ull;
+    RT_TRY(c, c->order.perm.alloc(bytes));
+    RT_TRY(c, c->order.h_perm.alloc(bytes));
   }
-  std::memcpy(c->h_perm.get(), perm.data(), bytes);
-  RT_TRY(c, hipMemcpyAsync(c->perm.get(), c->h_perm.get(), bytes, hipMemcpyHostToDevice, c->stream));
-  c->perm_view = v;
-  c->perm_gen = c->scene_gen;
-  for (int k = 0; k < kSchedClasses; k++) c->perm_cls[k] = cls[k];
-  out = c->perm.get();
-  c->perm_builds++;
-  c->perm_build_ms += ms_since(t0);
+  std::memcpy(c->order.h_perm.get(), perm.data(), bytes);
+  RT_TRY(c, hipMemcpyAsync(c->order.perm.get(), c->order.h_perm.get(), bytes, hipMemcpyHostToDevice, c->stream));
+  c->order.view = v;
+  c->order.gen = c->scene_gen;
+  for (int k = 0; k < kSchedClasses; k++) c->order.cls[k] = cls[k];
+  out = c->order.perm.get();
+  c->info.perm_builds++;
+  c->info.perm_build_ms += ms_since(t0);
   return RT_OK;
 }
 
 // (Re-)records the launch's start event just before its first kernel: the
 // host-side builds a launch may make first (tile order, camera grid) are not
 // kernel time.  enqueue() has recorded it already for launches with no kernel.
-hipError_t mark_start(rt_ctx *c) { return hipEventRecord(c->ev0[(int)(c->launches % rt_ctx::kRing)], c->stream); }
+hipError_t mark_start(rt_ctx *c) { return hipEventRecord(c->timing.ev0[c->timing.slot()], c->stream); }
 
 // Which render kernel a launch runs: the scene staged in LDS or read through
 // L2, the cull sweeps, 1 or 4 samples, kStackGlobal or kStackMerge; fast /
@@ -2899,6 +2940,7 @@ struct KernelSel {
   bool lds, cull;
   int samples, stack;
   bool fast = false, wide = false;
+  int merge_q = 64;  // kStackMerge: the LDS ray-queue entries per wave launch_render picked (no other kernel reads it)
 };
 
 // The two tables of kernel instantiations: every render and deferred kernel
@@ -2933,193 +2975,226 @@ const void *deferred_kernel_fn(const KernelSel &s, bool walk, bool wide) {
 #undef RT_RD
 }
 
-int launch_tiles(rt_ctx *c, KernelSel sel, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
-                 const OutDesc &od) {
-  Scene &scn = c->scene;
-  BvhArgs bv = bvh_args(c, cam);
-  const LgArgs lg = lg_args(c);
-  const bool merge = sel.stack == kStackMerge;
-  const int kWg = sel.lds ? wg_waves<true>() : wg_waves<false>(), kWx = kWg == 4 ? 2 : 1, kWy = kWg / kWx;
-  // the ordered walk's stacks follow the scene in LDS (render_kernel)
-  if (bv.ordered)
-    bv.ostk_off = (int)((lds_layout(sel.lds, scn.nsph, scn.nlight, bv.nnodes).end + 31) & ~(size_t)31);
-  const int ntx = (od.xw + 8 * kWx - 1) / (8 * kWx), nty = (rows.count + 8 * kWy - 1) / (8 * kWy);
-  const long long ntiles = (long long)ntx * nty;
-  // frames of this launch (rt_render_frames_async)
-  const int nf = c->nframes;
-  if (nf < 1 || nf > RT_MAX_FRAMES) return RT_ERR_INVALID_ARG;
-  // kStackMerge: one wave per kMergeTiles consecutive tile slots
-  long long nslots = merge ? (ntiles + kMergeTiles - 1) / kMergeTiles : ntiles;
-  if (ntiles * nf > (1LL << 30)) return RT_ERR_INVALID_ARG;
-  // rt_render_tiles: the launch visits the blocks (launch tiles) that overlap
-  // a requested tile, in scanline order of the blocks
-  const int *batch_perm = nullptr;
-  if (!merge && c->req_tiles) {
-    const int bw = 8 * kWx, bh = 8 * kWy;
-    std::vector<unsigned char> mark((size_t)ntiles, 0);
-    for (int i = 0; i < c->req_n; i++) {
-      const rt_tile &t = c->req_tiles[i];
-      // in 64 bits: a caller's x + width near INT_MAX must still clip to the image
-      const int x1 = (int)std::min<long long>(W, (long long)t.x + t.width);
-      const int j1 = (int)std::min<long long>(H, (long long)t.y + t.height);
-      if (t.x >= x1 || t.y >= j1) continue;
-      // framebuffer rows j (0 = bottom) are PPM rows H-1-j
-      const int y0 = H - j1, y1 = H - 1 - t.y;
-      for (int by = y0 / bh; by <= y1 / bh; by++)
-        for (int bx = t.x / bw; bx <= (x1 - 1) / bw; bx++) mark[(size_t)by * ntx + bx] = 1;
-    }
-    std::vector<int> list;
-    for (long long b = 0; b < ntiles; b++)
-      if (mark[(size_t)b]) list.push_back((int)b);
-    nslots = (long long)list.size();
-    if (nslots == 0) return RT_OK;
-    const size_t bytes = list.size() * sizeof(int);
-    RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous list may still be in flight from h_bperm
-    if (c->bperm.bytes() < bytes || c->h_bperm.bytes() < bytes) {  // grow-only, the pair together
-      RT_TRY(c, c->bperm.alloc(bytes));
-      RT_TRY(c, c->h_bperm.alloc(bytes));
-    }
-    std::memcpy(c->h_bperm.get(), list.data(), bytes);
-    RT_TRY(c, hipMemcpyAsync(c->bperm.get(), c->h_bperm.get(), bytes, hipMemcpyHostToDevice, c->stream));
-    batch_perm = c->bperm.get();
+int wg_waves_of(bool lds_geo) { return lds_geo ? wg_waves<true>() : wg_waves<false>(); }
+
+// The dynamic LDS of a render launch as render_kernel lays it out from the
+// same arguments: the staged scene (lds_layout), the ordered walk's stacks at
+// ostk_off, then at pix_off the parked colours (trace_wave) or, for merged
+// levels, the wave's ray queue of merge_q entries and finished pixels
+// (merge_tiles).
+struct LdsPlan {
+  size_t scene_end, ostk_off, pix_off, total;
+};
+LdsPlan lds_plan(const Scene &scn, const BvhArgs &bv, bool lds_geo, bool merge, int merge_q) {
+  const size_t wg = (size_t)wg_waves_of(lds_geo);
+  LdsPlan p;
+  p.scene_end = lds_layout(lds_geo, scn.nsph, scn.nlight, bv.nnodes).end;
+  p.ostk_off = (p.scene_end + 31) & ~(size_t)31;
+  p.pix_off = p.ostk_off + (bv.ordered ? wg * bv.odepth * 64 * sizeof(int2) : 0);
+  p.total = p.pix_off;
+  if (!lds_geo && !merge) p.total += wg * 64 * sizeof(D3);
+  if (merge) p.total += (size_t)merge_q * sizeof(QRay) + kPixbufBytes;
+  return p;
+}
+
+// rt_render_tiles: the blocks (launch tiles of bw x bh pixels, ntx per row)
+// that overlap a requested tile, in scanline order of the blocks, copied to
+// the device (`out`); n of them, 0: nothing to launch.
+int block_list(rt_ctx *c, const LaunchReq &q, int bw, int bh, int ntx, long long ntiles, const int *&out,
+               long long &n) {
+  std::vector<unsigned char> mark((size_t)ntiles, 0);
+  for (int i = 0; i < q.ntiles; i++) {
+    const rt_tile &t = q.tiles[i];
+    // in 64 bits: a caller's x + width near INT_MAX must still clip to the image
+    const int x1 = (int)std::min<long long>(q.W, (long long)t.x + t.width);
+    const int j1 = (int)std::min<long long>(q.H, (long long)t.y + t.height);
+    if (t.x >= x1 || t.y >= j1) continue;
+    // framebuffer rows j (0 = bottom) are PPM rows H-1-j
+    const int y0 = q.H - j1, y1 = q.H - 1 - t.y;
+    for (int by = y0 / bh; by <= y1 / bh; by++)
+      for (int bx = t.x / bw; bx <= (x1 - 1) / bw; bx++) mark[(size_t)by * ntx + bx] = 1;
   }
-  D3 amb{scn.amb[0], scn.amb[1], scn.amb[2]};
-  lds = (lds + 31) & ~(size_t)31;
-  // the kernel places the ordered walk's stacks from these same arguments
-  if (bv.ordered)
-    lds += (size_t)kWg * bv.odepth * 64 * sizeof(int2);
-  if (!sel.lds && !merge) lds += (size_t)kWg * 64 * sizeof(D3);  // parked colours (trace_wave)
-  if (merge)  // the wave's ray queue and finished pixels (merge_tiles)
-    lds += (size_t)c->merge_q * sizeof(QRay) + kPixbufBytes;
+  std::vector<int> list;
+  for (long long b = 0; b < ntiles; b++)
+    if (mark[(size_t)b]) list.push_back((int)b);
+  n = (long long)list.size();
+  if (n == 0) return RT_OK;
+  const size_t bytes = list.size() * sizeof(int);
+  RT_TRY(c, hipStreamSynchronize(c->stream));  // the previous list may still be in flight from h_bperm
+  if (c->bperm.bytes() < bytes || c->h_bperm.bytes() < bytes) {  // grow-only, the pair together
+    RT_TRY(c, c->bperm.alloc(bytes));
+    RT_TRY(c, c->h_bperm.alloc(bytes));
+  }
+  std::memcpy(c->h_bperm.get(), list.data(), bytes);
+  RT_TRY(c, hipMemcpyAsync(c->bperm.get(), c->h_bperm.get(), bytes, hipMemcpyHostToDevice, c->stream));
+  out = c->bperm.get();
+  return RT_OK;
+}
+
+// How a launch's tiles go to wave slots: `perm` their order (nullptr:
+// scanline), the first nsingle a wave each, the last `tail` too, the rest
+// kMergeTiles per wave; nslots wave slots per frame.
+struct SlotPlan {
+  const int *perm = nullptr;
+  int nsingle = 0;
+  long long tail = 0, nslots = 0;
+};
+
+// kStackMerge with a tile order of `cls` tiles per class, the heaviest classes
+// leading it: one wave per tile for them.
+SlotPlan slot_plan(const long long *cls, long long ntiles, int nf, const Knobs &k, int n_cu) {
+  SlotPlan s;
+  // one-frame launches: the tiles under reflective spheres (class >= 1) a
+  // wave each, the rest four per wave, the last ones (tail) single again
+  // (synth200 0.314 -> 0.298 ms, complex 0.293 -> 0.286 against every tile
+  // single, profiles/r5g/); multi-frame launches merge every class
+  const int sc = k.single_class >= 0 ? k.single_class : (nf == 1 ? 1 : kSchedClasses);
+  long long heavy = 0;
+  for (int i = sc; i < kSchedClasses; i++) heavy += cls[i];
+  s.nsingle = (int)std::min<long long>(heavy, ntiles);
+  // multi-frame launches end on their lightest tiles one per wave: about
+  // as many as the chip holds waves (12 per CU), over the launch's frames
+  if (k.tail) s.tail = std::min<long long>(ntiles - s.nsingle, ((long long)n_cu * k.tail_waves + nf - 1) / nf);
+  s.nslots = s.nsingle + (ntiles - s.nsingle - s.tail + kMergeTiles - 1) / kMergeTiles + s.tail;
+  return s;
+}
+
+// kStackMerge: the deferred queue of a launch that defers (ra.dq, dq_cap,
+// dstack; none otherwise).
+void defer_room(rt_ctx *c, const LaunchReq &q, RenderArgs &ra) {
+  const int nf = q.nframes, depth = q.depth;
+  if (!(c->knobs.defer > 0 || (c->knobs.defer < 0 && nf > 1)) || depth <= c->knobs.defer_level) return;
+  // room for 1/8 of the launch's pixels (deferred rays are ~2 % on synth200); a ray
+  // that finds its shard segment full simply continues in its merge_tiles lane.
+  // Each queue slot has its chain's stack after the queue: [depth-1][kShards * cap]
+  const size_t npx = (size_t)q.rows.count * q.od.xw * nf;
+  const size_t cap = std::max<size_t>(64, ((npx / kShards / (size_t)c->knobs.defer_div) + 63) & ~(size_t)63);
+  const size_t need = cap * kShards * (sizeof(QRay) + (size_t)(depth - 1) * sizeof(StackEnt));
+  // the queue is a speed-up: past the 32-bit slot-stack index, or when the
+  // memory is not there (grow_soft), the launch runs without deferral
+  if (cap < (size_t)1 << 30 && (unsigned long long)cap * kShards * (unsigned)(depth - 1) < (1ull << 32) &&
+      grow_soft(c, c->dq, need)) {
+    ra.dq = c->dq.get();
+    ra.dq_cap = (int)cap;
+    ra.dstack = reinterpret_cast<StackEnt *>(c->dq.get() + cap * kShards);
+  }
+}
+
+// kStackMerge: the stack homes (ra.homes, home_bits, home_words), 2 x the
+// resident waves of render kernel kf with `lds` bytes of LDS per workgroup of wg waves.
+int stack_homes(rt_ctx *c, const void *kf, int wg, size_t lds, int depth, RenderArgs &ra) {
+  if (kf != c->occ.kernel || lds != c->occ.lds) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * wg, lds) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 32;  // the most waves a CU holds
+    }
+    c->occ = OccCache{kf, lds, nb};
+  }
+  const size_t words = (size_t)(((long long)2 * c->occ.blocks * wg * c->n_cu + 63) / 64);
+  const size_t hb = words * 64 * (size_t)(depth - 1) * kHomePx * sizeof(StackEnt);
+  const size_t wb = words * sizeof(unsigned long long);
+  if (c->homes.bytes() < hb || c->home_bits.bytes() < wb) {
+    RT_TRY(c, hipStreamSynchronize(c->stream));  // launches in flight hold homes
+    c->homes.reset(), c->home_bits.reset();      // both go, whichever was too small
+    RT_TRY(c, c->homes.alloc(hb));
+    RT_TRY(c, c->home_bits.alloc(wb));
+    // zero once: every wave returns the home it took, so a drained launch leaves the bitmap zero
+    RT_TRY(c, hipMemset(c->home_bits.get(), 0, wb));
+  }
+  ra.homes = c->homes.get();
+  ra.home_bits = c->home_bits.get();
+  ra.home_words = (int)(c->home_bits.bytes() / sizeof(unsigned long long));
+  return RT_OK;
+}
+
+// The kernels' argument block of a launch, but for what launch_tiles adds
+// when it has it: the deferred queue, the stack homes, the camera and sphere grids.
+RenderArgs render_args(const rt_ctx *c, const LaunchReq &q, const Cam &cam, const KernelSel &sel, const BvhArgs &bv,
+                       const LdsPlan &lp, int ntx, long long ntiles, const SlotPlan &sp, StackEnt *gstack) {
+  const Scene &scn = c->scene;
+  const int nf = q.nframes;
+  RenderArgs ra{};
+  ra.geo = scn.geo.get(), ra.radius = scn.rad.get(), ra.mat = scn.mat.get(), ra.lights = scn.lights.get();
+  ra.n = scn.nsph, ra.nl = scn.nlight;
+  ra.amb = D3{scn.amb[0], scn.amb[1], scn.amb[2]};
+  ra.cam[0] = cam;
+  for (int f = 1; f < nf; f++) ra.cam[f] = to_cam(q.cams[f]);
+  ra.frames = nf;
+  ra.W = q.W, ra.H = q.H, ra.depth = q.depth, ra.rows = q.rows, ra.od = q.od;
+  ra.bv = bv;
+  ra.lg = lg_args(c);
+  ra.gstack = gstack;
+  ra.counters = c->ctr.cur;
+  ra.ntx = ntx, ra.ntiles = (int)ntiles, ra.nslots = (int)sp.nslots, ra.perm = sp.perm;
+  // zero the other counter half for the next launch (enqueue's alternation)
+  const int next = (int)((c->timing.launches + 1) & 1);
+  ra.zero_next = c->ctr.base.get() + (size_t)next * kShards * kShardStride;
+  ra.merge_q = sel.merge_q, ra.nsingle = sp.nsingle, ra.merge_end = (int)(ntiles - sp.tail);
+  // merge_tiles' pixel bytes: after the scene and the walk stacks, where render_kernel's park/queue region starts
+  ra.pix_off = (int)lp.pix_off;
+  // row k of frame f starts at ptr + f fstride + 3 (k W + x): dword aligned for every k, f and x = 8i
+  ra.rows_dword =
+      ((reinterpret_cast<uintptr_t>(q.od.ptr) | (uintptr_t)(3 * (size_t)q.W) | (uintptr_t)q.od.fstride) & 3) == 0;
+  ra.defer_level = c->knobs.defer_level;
+  ra.xcd_frames = (nf > 1 && (c->knobs.xcd_frames > 0 || (c->knobs.xcd_frames < 0 && bv.ug.on))) ? 1 : 0;
+  return ra;
+}
+
+// What a launch put on the stream, for enqueue's bookkeeping: a render kernel (it zeroes
+// the other counter half), whether it used camera grids (of cg_n cells) / the behind grid.
+struct Launched {
+  bool kernel = false, cg = false, ug = false;
+  int cg_n = 0;
+};
+
+int launch_tiles(rt_ctx *c, const LaunchReq &q, KernelSel sel, const Cam &cam, BvhArgs bv, Launched &did) {
+  Scene &scn = c->scene;
+  const int nf = q.nframes, depth = q.depth;
+  const bool merge = sel.stack == kStackMerge;
+  const int kWg = wg_waves_of(sel.lds), kWx = kWg == 4 ? 2 : 1, kWy = kWg / kWx;
+  const LdsPlan lp = lds_plan(scn, bv, sel.lds, merge, sel.merge_q);
+  // the ordered walk's stacks follow the scene in LDS (render_kernel)
+  if (bv.ordered) bv.ostk_off = (int)lp.ostk_off;
+  const int ntx = (q.od.xw + 8 * kWx - 1) / (8 * kWx), nty = (q.rows.count + 8 * kWy - 1) / (8 * kWy);
+  const long long ntiles = (long long)ntx * nty;
+  if (ntiles * nf > (1LL << 30)) return RT_ERR_INVALID_ARG;
+  int rc = RT_OK;
+  SlotPlan sp;
+  // kStackMerge: one wave per kMergeTiles consecutive tile slots
+  sp.nslots = merge ? (ntiles + kMergeTiles - 1) / kMergeTiles : ntiles;
+  if (!merge && q.tiles)
+    if ((rc = block_list(c, q, 8 * kWx, 8 * kWy, ntx, ntiles, sp.perm, sp.nslots)) != RT_OK || sp.nslots == 0) return rc;
   StackEnt *gstack = nullptr;
   if (depth > 1 && !merge) {
     // the kernel indexes the stack with 32 bits: entry + level * npx < 2^32
-    if ((unsigned long long)(depth - 1) * rows.count * od.xw * nf >= (1ull << 32)) return RT_ERR_INVALID_ARG;
+    if ((unsigned long long)(depth - 1) * q.rows.count * q.od.xw * nf >= (1ull << 32)) return RT_ERR_INVALID_ARG;
     // grow-only: sized for this launch's frames; a later launch of as many
     // frames or fewer (a last partial batch) reuses it
-    const int rc = grow(c, c->gstack, (size_t)(depth - 1) * rows.count * od.xw * nf * sizeof(StackEnt));
-    if (rc != RT_OK) return rc;
+    if ((rc = grow(c, c->gstack, (size_t)(depth - 1) * q.rows.count * q.od.xw * nf * sizeof(StackEnt))) != RT_OK) return rc;
     gstack = c->gstack.get();
   }
-  const int *perm = nullptr;
-  int nsingle = 0;
-  long long tail = 0;
   // The heavy-first order pays off when a launch has many more tiles than the
   // chip has wave slots; a small launch (a hybrid driver's 64x64 tile) keeps
   // scanline order and skips building and uploading one (which waits for the
   // stream whenever the tile shape changes).
-  if (batch_perm) {
-    perm = batch_perm;
-  } else if (c->sched && ntiles >= kSchedMinTiles) {
-    int rc = tile_perm(c, cam, W, H, rows, od, 8 * kWx, 8 * kWy, ntiles, perm);
-    if (rc != RT_OK) return rc;
-    if (merge) {  // the heaviest classes lead the order: one wave per tile for them
-      // one-frame launches: the tiles under reflective spheres (class >= 1) a
-      // wave each, the rest four per wave, the last ones (tail) single again
-      // (synth200 0.314 -> 0.298 ms, complex 0.293 -> 0.286 against every tile
-      // single, profiles/r5g/); multi-frame launches merge every class
-      const int sc = c->single_class >= 0 ? c->single_class : (nf == 1 ? 1 : kSchedClasses);
-      long long heavy = 0;
-      for (int k = sc; k < kSchedClasses; k++) heavy += c->perm_cls[k];
-      nsingle = (int)std::min<long long>(heavy, ntiles);
-      // multi-frame launches end on their lightest tiles one per wave: about
-      // as many as the chip holds waves (12 per CU), over the launch's frames
-      if (c->tail)
-        tail = std::min<long long>(ntiles - nsingle, ((long long)c->n_cu * c->tail_waves + nf - 1) / nf);
-      nslots = nsingle + (ntiles - nsingle - tail + kMergeTiles - 1) / kMergeTiles + tail;
-    }
+  if (!sp.perm && c->knobs.sched && ntiles >= kSchedMinTiles) {
+    const int *perm = nullptr;
+    if ((rc = tile_perm(c, q, cam, 8 * kWx, 8 * kWy, ntiles, perm)) != RT_OK) return rc;
+    if (merge) sp = slot_plan(c->order.cls, ntiles, nf, c->knobs, c->n_cu);
+    sp.perm = perm;
   }
-  const bool xcd_frames = nf > 1 && (c->xcd_frames > 0 || (c->xcd_frames < 0 && bv.ug.on));
-  const dim3 grid((unsigned)((xcd_frames ? (nslots + 7) / 8 * 8 : nslots) * nf));
-  RenderArgs ra{};
-  ra.geo = scn.geo.get();
-  ra.radius = scn.rad.get();
-  ra.mat = scn.mat.get();
-  ra.lights = scn.lights.get();
-  ra.n = scn.nsph;
-  ra.nl = scn.nlight;
-  ra.amb = amb;
-  ra.cam[0] = cam;
-  for (int f = 1; f < nf; f++) ra.cam[f] = to_cam(c->fcams[f]);
-  ra.frames = nf;
-  ra.W = W;
-  ra.H = H;
-  ra.depth = depth;
-  ra.rows = rows;
-  ra.bv = bv;
-  c->ug_last = bv.ug.on != 0;
-  ra.lg = lg;
-  ra.od = od;
-  ra.gstack = gstack;
-  ra.counters = c->d_counters;
-  ra.ntx = ntx;
-  ra.ntiles = (int)ntiles;
-  ra.nslots = (int)nslots;
-  ra.perm = perm;
-  // zero the other counter half for the next launch (enqueue's alternation)
-  const int next = (int)((c->launches + 1) & 1);
-  ra.zero_next = c->ctr_base.get() + (size_t)next * kShards * kShardStride;
-  c->zero_pending = true;
-  ra.dq = nullptr;
-  ra.dq_cap = 0;
-  ra.merge_q = c->merge_q;
-  ra.nsingle = nsingle;
-  ra.merge_end = (int)(ntiles - tail);
-  // merge_tiles' pixel bytes: after the scene and the walk stacks, where render_kernel's park/queue region starts
-  ra.pix_off = (int)(((lds_layout(sel.lds, scn.nsph, scn.nlight, bv.nnodes).end + 31) & ~(size_t)31) +
-                     (bv.ordered ? (size_t)kWg * bv.odepth * 64 * sizeof(int2) : 0));
-  // row k of frame f starts at ptr + f fstride + 3 (k W + x): dword aligned for every k, f and x = 8i
-  ra.rows_dword = ((reinterpret_cast<uintptr_t>(od.ptr) | (uintptr_t)(3 * (size_t)W) | (uintptr_t)od.fstride) & 3) == 0;
-  ra.defer_level = c->defer_level;
-  ra.xcd_frames = xcd_frames ? 1 : 0;
-  if (merge && (c->defer > 0 || (c->defer < 0 && nf > 1)) && depth > c->defer_level) {
-    // room for 1/8 of the launch's pixels (deferred rays are ~2 % on synth200); a ray
-    // that finds its shard segment full simply continues in its merge_tiles lane.
-    // Each queue slot has its chain's stack after the queue: [depth-1][kShards * cap]
-    const size_t npx = (size_t)rows.count * od.xw * nf;
-    const size_t cap = std::max<size_t>(64, ((npx / kShards / (size_t)c->defer_div) + 63) & ~(size_t)63);
-    const size_t need = cap * kShards * (sizeof(QRay) + (size_t)(depth - 1) * sizeof(StackEnt));
-    // the queue is a speed-up: past the 32-bit slot-stack index, or when the
-    // memory is not there (grow_soft), the launch runs without deferral
-    if (cap < (size_t)1 << 30 && (unsigned long long)cap * kShards * (unsigned)(depth - 1) < (1ull << 32) &&
-        grow_soft(c, c->dq, need)) {
-      ra.dq = c->dq.get();
-      ra.dq_cap = (int)cap;
-      ra.dstack = reinterpret_cast<StackEnt *>(c->dq.get() + cap * kShards);
-    }
-  }
+  RenderArgs ra = render_args(c, q, cam, sel, bv, lp, ntx, ntiles, sp, gstack);
+  const dim3 grid((unsigned)((ra.xcd_frames ? (sp.nslots + 7) / 8 * 8 : sp.nslots) * nf));
+  if (merge) defer_room(c, q, ra);
   // the default configuration (ordered 4-wide BVH walk, light grids) has kernels
   // compiled with only those paths (kFast): no registers held for the others
-  sel.fast = merge && bv.ordered && bv.wide && lg.on;
+  sel.fast = merge && bv.ordered && bv.wide && ra.lg.on;
   // the light loop of sparse waves spread over the lanes (shade_hit kWide, the default)
-  sel.wide = sel.fast && (c->wide_mode >= 2 || (nf == 1 && c->wide_mode == 1));
+  sel.wide = sel.fast && (c->knobs.wide_mode >= 2 || (nf == 1 && c->knobs.wide_mode == 1));
   const void *const kf = render_kernel_fn(sel);
-  if (merge && depth > 1) {  // the stack homes: 2 x the render kernel's resident waves
-    if (kf != c->occ_kernel || lds != c->occ_lds) {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf, 64 * kWg, lds) != hipSuccess || nb < 1) {
-        (void)hipGetLastError();
-        nb = 32;  // the most waves a CU holds
-      }
-      c->occ_kernel = kf;
-      c->occ_lds = lds;
-      c->occ_blocks = nb;
-    }
-    const size_t words = (size_t)(((long long)2 * c->occ_blocks * kWg * c->n_cu + 63) / 64);
-    const size_t hb = words * 64 * (size_t)(depth - 1) * kHomePx * sizeof(StackEnt);
-    const size_t wb = words * sizeof(unsigned long long);
-    if (c->homes.bytes() < hb || c->home_bits.bytes() < wb) {
-      RT_TRY(c, hipStreamSynchronize(c->stream));  // launches in flight hold homes
-      c->homes.reset(), c->home_bits.reset();      // both go, whichever was too small
-      RT_TRY(c, c->homes.alloc(hb));
-      RT_TRY(c, c->home_bits.alloc(wb));
-      // zero once: every wave returns the home it took, so a drained launch leaves the bitmap zero
-      RT_TRY(c, hipMemset(c->home_bits.get(), 0, wb));
-    }
-    ra.homes = c->homes.get();
-    ra.home_bits = c->home_bits.get();
-    ra.home_words = (int)(c->home_bits.bytes() / sizeof(unsigned long long));
-  }
+  const size_t lds = lp.total;
+  if (merge && depth > 1 && (rc = stack_homes(c, kf, kWg, lds, depth, ra)) != RT_OK) return rc;
   // the sphere grids, lazily (sg_pending): the scene's first multi-frame
   // launch or its second launch builds them, before the launch's timing
   // (a speed-up: if its build fails the launch runs without the grids)
@@ -3136,97 +3211,98 @@ int launch_tiles(rt_ctx *c, KernelSel sel, size_t lds, const Cam &cam, int W, in
   // launch's timing starts after it: the grids' device passes ahead of the
   // render kernel are part of the launch
   CgPlan plan;
-  if (sel.fast && sel.cull) {
-    const int rc = cam_grid_prepare(c, cam, nf, plan);
-    if (rc != RT_OK) return rc;
-  }
+  if (sel.fast && sel.cull && (rc = cam_grid_prepare(c, q, plan)) != RT_OK) return rc;
   RT_TRY(c, mark_start(c));
-  {
-    const int rc = cam_grid_enqueue(c, plan, ra.cg);
-    if (rc != RT_OK) return rc;
-  }
+  if ((rc = cam_grid_enqueue(c, plan, ra.cg)) != RT_OK) return rc;
   if (sel.fast && sel.cull && scn.sg_ok)
     ra.sg = SgArgs{scn.sg_start.get(), scn.sg_ent.get(), scn.sg_rho2.get(), scn.sg_n, 1,
                    scn.sg_nstart,      scn.sg_nent, scn.nsph};
-  c->cg_last = ra.cg.on != 0;
-  c->cg_last_n = ra.cg.on ? ra.cg.N : 0;
   void *args[] = {&ra};
   RT_TRY(c, hipLaunchKernel(kf, grid, dim3(64 * kWg), args, lds, c->stream));
+  did = Launched{true, ra.cg.on != 0, bv.ug.on != 0, ra.cg.on ? ra.cg.N : 0};
   if (ra.dq_cap > 0) {  // 48 one-wave workgroups per shard segment
     // the walk kernel where every closest hit walks the BVH anyway (large
     // scenes: synth10k 12.2 -> 11.0 ms per 8-frame launch); small scenes keep
     // the cull sweeps (synth200 1 % slower on the walk kernel); else the
     // deferred waves' tails spread their light loops too (wide_mode 3)
-    const bool walk = sel.cull && sel.fast && c->defer_walk && bv.nnodes > 0 && bv.always && !(bv.ug.on && bv.ug.closest);
-    RT_TRY(c, hipLaunchKernel(deferred_kernel_fn(sel, walk, sel.fast && c->wide_mode == 3),
+    const bool walk = sel.cull && sel.fast && c->knobs.defer_walk && bv.nnodes > 0 && bv.always &&
+                      !(bv.ug.on && bv.ug.closest);
+    RT_TRY(c, hipLaunchKernel(deferred_kernel_fn(sel, walk, sel.fast && c->knobs.wide_mode == 3),
                               dim3(RT_DEFER_WGS * kShards), dim3(64), args, lds, c->stream));
   }
   return RT_OK;
 }
 
-int launch_render(rt_ctx *c, bool lds_geo, size_t lds, const Cam &cam, int W, int H, int depth, const Rows &rows,
-                  const OutDesc &od) {
+int launch_render(rt_ctx *c, const LaunchReq &q, Launched &did) {
+  const Cam cam = to_cam(q.cams[0]);
+  const BvhArgs bv = bvh_args(c, cam);
+  const OutDesc &od = q.od;
+  // RT_HIP_LDS_SCENE: the scene and its BVH are staged in LDS when they fit (lds_layout)
+  const bool lds_geo =
+      c->knobs.lds_scene && lds_layout(true, c->scene.nsph, c->scene.nlight, bv.nnodes).end <= kLdsBudget;
   KernelSel sel{lds_geo, c->cull, c->samples == 4 ? 4 : 1, kStackGlobal};
   // merged reflection levels: RGB8 row-compact output, one sample, scene through L2,
   // and only while the wave's LDS (BVH stacks + ray queue) still allows the
   // 12 waves per CU its registers allow (synth10k's 22-entry stacks do not:
   // 10 waves, 12 % slower); otherwise the per-pixel global stack
-  if (c->stack_mode == kStackMerge && !sel.lds && sel.samples == 1 && od.fmt == RT_FB_RGB8 && !od.full && od.x0 == 0 &&
-      od.xw == W) {
-    const BvhArgs bv = bvh_args(c, cam);
-    const size_t stacks = bv.ordered ? (size_t)bv.odepth * 64 * sizeof(int2) : 0;
-    for (int q = c->merge_q_max; q >= 8; q /= 2)  // the longest queue that keeps 12 waves per CU
-      if (12 * (stacks + (size_t)q * sizeof(QRay) + kPixbufBytes + ((lds + 31) & ~(size_t)31)) <= 160 * 1024) {
-        c->merge_q = q;
+  if (c->knobs.stack_mode == kStackMerge && !sel.lds && sel.samples == 1 && od.fmt == RT_FB_RGB8 && !od.full &&
+      od.x0 == 0 && od.xw == q.W)
+    for (int mq = c->knobs.merge_q_max; mq >= 8; mq /= 2)  // the longest queue that keeps 12 waves per CU
+      if (12 * lds_plan(c->scene, bv, false, true, mq).total <= 160 * 1024) {
+        sel.merge_q = mq;
         sel.stack = kStackMerge;
         break;
       }
-  }
-  return launch_tiles(c, sel, lds, cam, W, H, depth, rows, od);
+  return launch_tiles(c, q, sel, cam, bv, did);
 }
 
-int validate(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows, const void *out,
-             Rows &r) {
-  if (!c || !cam || !out || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
+// The checks of every render entry point, in this order: arguments (`tiles`: the caller's
+// tiles, whose signs are checked), the scene, the depth, then the request's rows and frames.
+int validate(const rt_ctx *c, const LaunchReq &q, const rt_tile *tiles = nullptr, int ntiles = 0) {
+  if (!c || !q.cams || !q.od.ptr || q.W <= 0 || q.H <= 0 || ntiles < 0 || (ntiles > 0 && !tiles))
+    return RT_ERR_INVALID_ARG;
+  if (q.od.fmt != RT_FB_RGB8 && q.od.fmt != RT_FB_F32X3 && q.od.fmt != RT_FB_F64X3) return RT_ERR_INVALID_ARG;
+  for (int i = 0; i < ntiles; i++)
+    if (tiles[i].x < 0 || tiles[i].y < 0 || tiles[i].width < 0 || tiles[i].height < 0) return RT_ERR_INVALID_ARG;
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
-  r = rows ? Rows{rows->band, rows->first, rows->stride, rows->count} : Rows{1, 0, 1, H};
+  if (q.depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  const Rows &r = q.rows;
   if (r.band < 1 || r.stride < 1 || r.first < 0 || r.count < 0) return RT_ERR_INVALID_ARG;
-  if ((long long)W * 3 * (long long)r.count > (1LL << 40)) return RT_ERR_INVALID_ARG;
+  if (!q.od.full && (long long)q.W * 3 * (long long)r.count > (1LL << 40)) return RT_ERR_INVALID_ARG;
+  if (q.nframes < 1 || q.nframes > RT_MAX_FRAMES) return RT_ERR_INVALID_ARG;
+  const size_t fstride = (size_t)q.od.fstride;  // (as rt_render_frames_async was given it)
+  if (q.nframes > 1 && (fstride < (size_t)r.count * q.W * 3 || fstride > (size_t)1 << 62)) return RT_ERR_INVALID_ARG;
   return RT_OK;
 }
 
-int enqueue(rt_ctx *c, const rt_camera *cm, int W, int H, int depth, const Rows &r, const OutDesc &od) {
+Rows to_rows(const rt_rows *rows, int H) {  // nullptr: every row of the image
+  return rows ? Rows{rows->band, rows->first, rows->stride, rows->count} : Rows{1, 0, 1, H};
+}
+
+int enqueue(rt_ctx *c, const LaunchReq &q) {
   RT_TRY(c, hipSetDevice(c->device));
-  const int half = (int)(c->launches & 1);
-  c->d_counters = c->ctr_base.get() + (size_t)half * kShards * kShardStride;
-  if (!c->ctr_clean[half])
-    RT_TRY(c, hipMemsetAsync(c->d_counters, 0, kShards * kShardStride * sizeof(unsigned long long), c->stream));
-  c->ctr_clean[half] = false;
-  c->zero_pending = false;
-  const int slot = (int)(c->launches % rt_ctx::kRing);
-  RT_TRY(c, hipEventRecord(c->ev0[slot], c->stream));
-  c->cg_last = false;
-  c->cg_last_n = 0;
-  if (r.count > 0) {
-    const Cam cam = to_cam(*cm);
-    // the scene and its BVH are staged in LDS when they fit (lds_layout)
-    const Scene &scn = c->scene;
-    const int nn = (c->bvh_on && c->cull) ? scn.bvh_nodes : 0;
-    const bool lds_geo = c->lds_scene && lds_layout(true, scn.nsph, scn.nlight, nn).end <= kLdsBudget;
-    const size_t lds = lds_layout(lds_geo, scn.nsph, scn.nlight, nn).end;
-    if (lds > kLdsBudget) {
-      c->err = "light list does not fit in LDS";
-      return RT_ERR_INVALID_ARG;
-    }
-    int rc = launch_render(c, lds_geo, lds, cam, W, H, depth, r, od);
+  const int half = (int)(c->timing.launches & 1);
+  c->ctr.cur = c->ctr.base.get() + (size_t)half * kShards * kShardStride;
+  if (!c->ctr.clean[half])
+    RT_TRY(c, hipMemsetAsync(c->ctr.cur, 0, kShards * kShardStride * sizeof(unsigned long long), c->stream));
+  c->ctr.clean[half] = false;
+  const int slot = c->timing.slot();
+  RT_TRY(c, hipEventRecord(c->timing.ev0[slot], c->stream));
+  Launched did;
+  if (q.rows.count > 0) {
+    const int rc = launch_render(c, q, did);
     if (rc != RT_OK) return rc;
     RT_TRY(c, hipGetLastError());
   }
-  RT_TRY(c, hipEventRecord(c->ev1[slot], c->stream));
-  if (c->zero_pending) c->ctr_clean[(c->launches + 1) & 1] = true;
-  c->zero_pending = false;
-  c->launches++;
+  RT_TRY(c, hipEventRecord(c->timing.ev1[slot], c->stream));
+  // the launch is on the stream: what it leaves for the next one and for rt_get_info
+  if (did.kernel) {
+    c->ctr.clean[(c->timing.launches + 1) & 1] = true;
+    c->info.ug_last = did.ug;
+  }
+  c->info.cg_last = did.cg;
+  c->info.cg_last_n = did.cg_n;
+  c->timing.launches++;
   c->scene.launches++;
   return RT_OK;  // the counters are read back by rt_render_stats, after the stream drains
 }
@@ -3249,48 +3325,7 @@ int rt_create(int device, rt_ctx **out) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return RT_ERR_NO_DEVICE;
   if (device < 0 || device >= n) return RT_ERR_INVALID_ARG;
-  rt_ctx *c = new rt_ctx();
-  c->device = device;
-  // Environment knobs.  The product build reads two: RT_HIP_LDS_SCENE (the
-  // north star's sphere array and light list staged in LDS per workgroup) and
-  // RT_HIP_CAM_GRID (when the camera grid is built: 0 never, 1 auto, 2 for
-  // every launch).  The tuning build (-DRT_TUNING: variants/librt_hip_tuning.so)
-  // also reads the layout and grid knobs that the parity tests sweep and the
-  // A/B scripts measured; every default below is the measured optimum.
-  if (const char *e = std::getenv("RT_HIP_LDS_SCENE")) c->lds_scene = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_CAM_GRID")) c->cg_mode = std::max(0, std::min(2, std::atoi(e)));
-#ifdef RT_TUNING
-  if (const char *e = std::getenv("RT_HIP_BVH")) c->bvh_on = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_BVH_MIN")) c->bvh_min = std::atoi(e);
-  if (const char *e = std::getenv("RT_HIP_BVH_ALWAYS")) c->bvh_always = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_BVH_GROUPS")) c->bvh_groups = std::max(1, std::atoi(e));
-  if (const char *e = std::getenv("RT_HIP_SHADOW_GRID")) c->lg_on = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_SCHED")) c->sched = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_STACK")) c->stack_mode = std::atoi(e) == kStackGlobal ? kStackGlobal : kStackMerge;
-  if (const char *e = std::getenv("RT_HIP_BVH_ORDERED")) c->bvh_ordered = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_BVH4")) c->bvh_wide = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_BVH_LEAF")) c->bvh_leaf_opt = std::max(1, std::min(15, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_DEFER")) c->defer = std::atoi(e) != 0 ? 1 : 0;
-  if (const char *e = std::getenv("RT_HIP_DEFER_WALK")) c->defer_walk = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_DEFER_LEVEL")) c->defer_level = std::max(1, std::min(RT_MAX_DEPTH, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_MERGE_Q")) c->merge_q_max = std::max(8, std::min(64, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_SHADOW_GRID_N")) c->lg_n_opt = std::max(1, std::min(1024, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_CAM_GRID_N")) c->cg_n_opt = std::max(1, std::min(1024, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_CAM_GRID_BUDGET")) c->cg_budget_opt = std::max(0LL, std::atoll(e));
-  if (const char *e = std::getenv("RT_HIP_CAM_GRID_MAXP")) c->cg_maxp_opt = std::max(1LL, std::atoll(e));
-  if (const char *e = std::getenv("RT_HIP_SPHERE_GRID")) c->sg_mode = std::max(-1, std::min(1, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_SPHERE_GRID_N")) c->sg_n_opt = std::max(1, std::min(256, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_BEHIND_GRID")) c->ug_mode = std::max(-1, std::min(1, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_GRID_CLOSEST")) c->ug_closest = std::atoi(e) != 0 ? 1 : 0;  // (see ug_closest)
-  if (const char *e = std::getenv("RT_HIP_XCD_FRAMES")) c->xcd_frames = std::max(-1, std::min(1, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_TAIL")) c->tail = std::atoi(e) != 0;
-  if (const char *e = std::getenv("RT_HIP_TAIL_WAVES")) c->tail_waves = std::max(1, std::min(64, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_WIDE")) c->wide_mode = std::max(0, std::min(3, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_DEFER_DIV")) c->defer_div = std::max(1, std::min(1024, std::atoi(e)));
-  if (const char *e = std::getenv("RT_HIP_GRID_CELLS")) c->ug_cells = std::max(0.05, std::min(64.0, std::atof(e)));
-  if (const char *e = std::getenv("RT_HIP_SINGLE_CLASS"))
-    c->single_class = std::max(0, std::min(kSchedClasses, std::atoi(e)));
-#endif
+  rt_ctx *c = new rt_ctx(device, read_knobs());
   auto bail = [&](int rc) {
     rt_destroy(c);
     return rc;
@@ -3308,15 +3343,15 @@ int rt_create(int device, rt_ctx **out) {
   if (hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault) != hipSuccess) return bail(RT_ERR_HIP);
   if (hipEventCreateWithFlags(&c->switch_ev, hipEventDisableTiming) != hipSuccess) return bail(RT_ERR_HIP);
   c->stream = c->own_stream;
-  if (c->ctr_base.alloc(2 * kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
+  if (c->ctr.base.alloc(2 * kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
     return bail(RT_ERR_OUT_OF_MEMORY);
-  if (hipMemset(c->ctr_base.get(), 0, c->ctr_base.bytes()) != hipSuccess) return bail(RT_ERR_HIP);
-  c->d_counters = c->ctr_base.get();
-  if (c->h_counters.alloc(kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
+  if (hipMemset(c->ctr.base.get(), 0, c->ctr.base.bytes()) != hipSuccess) return bail(RT_ERR_HIP);
+  c->ctr.cur = c->ctr.base.get();
+  if (c->ctr.host.alloc(kShards * kShardStride * sizeof(unsigned long long)) != hipSuccess)
     return bail(RT_ERR_OUT_OF_MEMORY);
-  std::memset(c->h_counters.get(), 0, c->h_counters.bytes());
-  for (int i = 0; i < rt_ctx::kRing; i++)
-    if (hipEventCreate(&c->ev0[i]) != hipSuccess || hipEventCreate(&c->ev1[i]) != hipSuccess) return bail(RT_ERR_HIP);
+  std::memset(c->ctr.host.get(), 0, c->ctr.host.bytes());
+  for (int i = 0; i < LaunchTiming::kRing; i++)
+    if (hipEventCreate(&c->timing.ev0[i]) != hipSuccess || hipEventCreate(&c->timing.ev1[i]) != hipSuccess) return bail(RT_ERR_HIP);
   // The HIP runtime's one-time work in a process, done here rather than
   // inside the first render: the kernels' code object loads at the first
   // launch, and the first blocking host-to-device copy, the first large
@@ -3353,9 +3388,9 @@ void rt_destroy(rt_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
-  for (int i = 0; i < rt_ctx::kRing; i++) {
-    if (c->ev0[i]) (void)hipEventDestroy(c->ev0[i]);
-    if (c->ev1[i]) (void)hipEventDestroy(c->ev1[i]);
+  for (int i = 0; i < LaunchTiming::kRing; i++) {
+    if (c->timing.ev0[i]) (void)hipEventDestroy(c->timing.ev0[i]);
+    if (c->timing.ev1[i]) (void)hipEventDestroy(c->timing.ev1[i]);
   }
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -3396,7 +3431,7 @@ static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool wan
   RT_TRY(c, scn.pf.upload(st.pf, 1));
   RT_TRY(c, scn.bvh.upload(st.nodes, 1));
   RT_TRY(c, scn.prims.upload(st.prims, 1));
-  c->bvh_build_ms = st.bvh_ms + ms_since(t_bvh);
+  c->info.bvh_build_ms = st.bvh_ms + ms_since(t_bvh);
   if (want_ug) {
     const auto t_ug = std::chrono::steady_clock::now();
     if (st.ug_built) {
@@ -3415,16 +3450,11 @@ static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool wan
       scn.ug_entries = ug.ids.size();
       scn.ug_ok = true;
     }
-    c->ug_build_ms = st.ug_ms + ms_since(t_ug);
+    c->info.ug_build_ms = st.ug_ms + ms_since(t_ug);
   }
-  scn.bvh_nodes = (int)st.nodes.size();
-  scn.bvh2_nodes = (int)st.nodes2.size();
-  scn.bvh4_nodes = (int)st.nodes4.size();
+  scn.bvh_nodes = (int)st.nodes.size(), scn.bvh2_nodes = (int)st.nodes2.size(), scn.bvh4_nodes = (int)st.nodes4.size();
   scn.bvh_prims = (int)st.prims.size();
-  scn.bvh2_root = st.root2;
-  scn.bvh_depth = st.depth2;
-  scn.bvh4_root = st.root4;
-  scn.bvh4_stack = st.stack4;
+  scn.bvh2_root = st.root2, scn.bvh_depth = st.depth2, scn.bvh4_root = st.root4, scn.bvh4_stack = st.stack4;
   for (int k = 0; k < 3; k++) {
     scn.c0[k] = st.c0[k];
     scn.lo[k] = st.lo[k];
@@ -3436,16 +3466,15 @@ static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool wan
   RT_TRY(c, scn.mat.upload(st.mat, 1));
   RT_TRY(c, scn.lights.upload(st.lights, 1));
   // built on the device from geo / rad
-  c->nsph_up = n;
   int rc = light_grids(c, s, st);
   if (rc != RT_OK) return rc;
   // the spheres' copy only where a grid may be built from it, until it has been
-  const bool sg_auto = c->sg_mode < 0 && n <= kSgMaxSpheres;
-  if (c->sg_mode > 0 || sg_auto) scn.sg_src.assign(s->spheres, s->spheres + n);
+  const bool sg_auto = c->knobs.sg_mode < 0 && n <= kSgMaxSpheres;
+  if (c->knobs.sg_mode > 0 || sg_auto) scn.sg_src.assign(s->spheres, s->spheres + n);
   scn.sg_diam = st.diam;
   scn.launches = 0;
   scn.sg_pending = sg_auto;
-  if (c->sg_mode > 0 && (rc = sphere_grids(c)) != RT_OK) return rc;
+  if (c->knobs.sg_mode > 0 && (rc = sphere_grids(c)) != RT_OK) return rc;
   scn.nsph = n;
   scn.nlight = s->num_lights;
   scn.refl = std::move(st.refl);
@@ -3463,11 +3492,11 @@ int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   const bool big = s->num_spheres > kBvhAlwaysAbove;
   // leaves of 2 spheres (+0.6..0.9 % over 4 on synth200 with the merged levels);
   // 1 above kBvhAlwaysAbove, where every closest hit walks (synth10k 4.37 -> 4.16 ms)
-  c->bvh_leaf = c->bvh_leaf_opt ? c->bvh_leaf_opt : (big ? 1 : 2);
-  c->lg_n = c->lg_n_opt ? c->lg_n_opt : (big ? 768 : 128);
-  const bool want_ug = c->ug_mode > 0 || (c->ug_mode < 0 && big);
+  c->scene.bvh_leaf = c->knobs.bvh_leaf_opt ? c->knobs.bvh_leaf_opt : (big ? 1 : 2);
+  c->scene.lg_n = c->knobs.lg_n_opt ? c->knobs.lg_n_opt : (big ? 768 : 128);
+  const bool want_ug = c->knobs.ug_mode > 0 || (c->knobs.ug_mode < 0 && big);
   StagedScene st;
-  stage_scene(s, c->bvh_leaf, want_ug, c->ug_cells, st);
+  stage_scene(s, c->scene.bvh_leaf, want_ug, c->knobs.ug_cells, st);
   const int rc = upload_staged(c, s, st, want_ug);
   if (rc != RT_OK) {
     free_scene(c);
@@ -3475,31 +3504,20 @@ int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   }
   c->scene_gen++;
   c->scene.has_scene = true;
-  c->upload_ms = ms_since(t_upload);
+  c->info.upload_ms = ms_since(t_upload);
   return RT_OK;
 }
 
 int rt_render_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows, uint8_t *out) {
-  Rows r;
-  int rc = validate(c, cam, W, H, depth, rows, out, r);
-  if (rc != RT_OK) return rc;
-  return enqueue(c, cam, W, H, depth, r, OutDesc{out, RT_FB_RGB8, 0, 0, W});
+  return rt_render_frames_async(c, cam, 1, W, H, depth, rows, out, 0);
 }
 
 int rt_render_frames_async(rt_ctx *c, const rt_camera *cams, int nframes, int W, int H, int depth,
                            const rt_rows *rows, uint8_t *out, size_t frame_stride) {
-  Rows r;
-  int rc = validate(c, cams, W, H, depth, rows, out, r);
-  if (rc != RT_OK) return rc;
-  if (nframes < 1 || nframes > RT_MAX_FRAMES) return RT_ERR_INVALID_ARG;
-  if (nframes > 1 && (frame_stride < (size_t)r.count * W * 3 || frame_stride > (size_t)1 << 62))
-    return RT_ERR_INVALID_ARG;
-  c->nframes = nframes;
-  c->fcams = cams;
-  rc = enqueue(c, cams, W, H, depth, r, OutDesc{out, RT_FB_RGB8, 0, 0, W, (long long)frame_stride});
-  c->nframes = 1;
-  c->fcams = nullptr;
-  return rc;
+  const LaunchReq q{cams, nframes, W, H, depth, to_rows(rows, H),
+                    OutDesc{out, RT_FB_RGB8, 0, 0, W, (long long)frame_stride}};
+  const int rc = validate(c, q);
+  return rc != RT_OK ? rc : enqueue(c, q);
 }
 
 int rt_render_stats(rt_ctx *c, rt_stats *st) {
@@ -3507,12 +3525,12 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
   RT_TRY(c, hipSetDevice(c->device));
   RT_TRY(c, hipStreamSynchronize(c->stream));
   float ms = 0.f;
-  if (c->launches > 0) {
-    const int slot = (int)((c->launches - 1) % rt_ctx::kRing);
-    RT_TRY(c, hipEventElapsedTime(&ms, c->ev0[slot], c->ev1[slot]));
+  if (c->timing.launches > 0) {
+    const int slot = (int)((c->timing.launches - 1) % LaunchTiming::kRing);
+    RT_TRY(c, hipEventElapsedTime(&ms, c->timing.ev0[slot], c->timing.ev1[slot]));
   }
-  const unsigned long long *hc = c->h_counters.get();
-  RT_TRY(c, hipMemcpy(c->h_counters.get(), c->d_counters, c->h_counters.bytes(), hipMemcpyDeviceToHost));
+  const unsigned long long *hc = c->ctr.host.get();
+  RT_TRY(c, hipMemcpy(c->ctr.host.get(), c->ctr.cur, c->ctr.host.bytes(), hipMemcpyDeviceToHost));
   unsigned long long sum[kCounters] = {};
   for (int sh = 0; sh < kShards; sh++)
     for (int q = 0; q < kCounters; q++) sum[q] += hc[sh * kShardStride + q];
@@ -3554,8 +3572,6 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
       }
     }
   }
-#endif
-#ifdef RT_STAMPS
   if (std::getenv("RT_HIP_STAMPS")) {  // diagnostic builds (-DRT_STAMPS) fill slots 8..14
     unsigned long long d[12] = {};
     for (int sh = 0; sh < kShards; sh++)
@@ -3585,23 +3601,21 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
 
 int rt_render(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows, uint8_t *out,
               int out_on_device, rt_stats *st) {
-  Rows r;
-  int rc = validate(c, cam, W, H, depth, rows, out, r);
+  LaunchReq q{cam, 1, W, H, depth, to_rows(rows, H), OutDesc{out, RT_FB_RGB8, 0, 0, W}};
+  int rc = validate(c, q);
   if (rc != RT_OK) return rc;
   RT_TRY(c, hipSetDevice(c->device));
-  size_t bytes = (size_t)r.count * W * 3;
-  uint8_t *dst = out;
+  const size_t bytes = (size_t)q.rows.count * W * 3;
   if (!out_on_device) {
     rc = grow(c, c->tmp, bytes);
     if (rc != RT_OK) return rc;
-    dst = c->tmp.get();
+    q.od.ptr = c->tmp.get();
   }
-  rc = enqueue(c, cam, W, H, depth, r, OutDesc{dst, RT_FB_RGB8, 0, 0, W});
+  rc = enqueue(c, q);
   if (rc != RT_OK) return rc;
-  if (!out_on_device && bytes) RT_TRY(c, hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (!out_on_device && bytes) RT_TRY(c, hipMemcpyAsync(out, q.od.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
   rt_stats tmp;
-  rc = rt_render_stats(c, st ? st : &tmp);
-  return rc;
+  return rt_render_stats(c, st ? st : &tmp);
 }
 
 int rt_set_antialias(rt_ctx *c, int samples) {
@@ -3612,82 +3626,68 @@ int rt_set_antialias(rt_ctx *c, int samples) {
 
 int rt_render_tile(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, int tile_x, int tile_y, int tile_w,
                    int tile_h, int fb_format, void *fb_device) {
-  if (!c || !cam || !fb_device || W <= 0 || H <= 0 || tile_w < 0 || tile_h < 0 || tile_x < 0 || tile_y < 0)
-    return RT_ERR_INVALID_ARG;
-  if (fb_format != RT_FB_RGB8 && fb_format != RT_FB_F32X3 && fb_format != RT_FB_F64X3) return RT_ERR_INVALID_ARG;
-  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
-  // the reference kernel clips the tile to the image (kernel.cu:103)
-  const int xe = (int)std::min<long long>(W, (long long)tile_x + tile_w);  // 64-bit: no overflow near INT_MAX
-  const int ye = (int)std::min<long long>(H, (long long)tile_y + tile_h);
-  const int xw = std::max(0, xe - tile_x), th = std::max(0, ye - tile_y);
+  const rt_tile t{tile_x, tile_y, tile_w, tile_h};
+  // the reference kernel clips the tile to the image (kernel.cu:103); in 64 bits: no overflow near INT_MAX
+  const long long xe = std::min<long long>(W, (long long)tile_x + tile_w), ye = std::min<long long>(H, (long long)tile_y + tile_h);
+  const int xw = (int)std::max(0LL, xe - tile_x), th = (int)std::max(0LL, ye - tile_y);
   // framebuffer rows j = tile_y .. ye-1 (j = 0 the bottom row) are PPM rows H-ye .. H-1-tile_y
-  const Rows r{1, H - ye, 1, xw > 0 ? th : 0};
-  RT_TRY(c, hipSetDevice(c->device));
-  return enqueue(c, cam, W, H, depth, r, OutDesc{fb_device, fb_format, 1, tile_x, xw});
+  const Rows r{1, (int)(H - ye), 1, xw > 0 ? th : 0};
+  const LaunchReq q{cam, 1, W, H, depth, r, OutDesc{fb_device, fb_format, 1, tile_x, xw}};
+  const int rc = validate(c, q, &t, 1);
+  return rc != RT_OK ? rc : enqueue(c, q);
 }
 
 int rt_render_tiles(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_tile *tiles, int ntiles,
                     int fb_format, void *fb_device) {
-  if (!c || !cam || !fb_device || W <= 0 || H <= 0 || ntiles < 0 || (ntiles > 0 && !tiles)) return RT_ERR_INVALID_ARG;
-  if (fb_format != RT_FB_RGB8 && fb_format != RT_FB_F32X3 && fb_format != RT_FB_F64X3) return RT_ERR_INVALID_ARG;
-  for (int i = 0; i < ntiles; i++)
-    if (tiles[i].x < 0 || tiles[i].y < 0 || tiles[i].width < 0 || tiles[i].height < 0) return RT_ERR_INVALID_ARG;
-  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
-  RT_TRY(c, hipSetDevice(c->device));
-  c->req_tiles = tiles;
-  c->req_n = ntiles;
-  const int rc = enqueue(c, cam, W, H, depth, Rows{1, 0, 1, H}, OutDesc{fb_device, fb_format, 1, 0, W});
-  c->req_tiles = nullptr;
-  c->req_n = 0;
-  return rc;
+  const LaunchReq q{cam, 1, W, H, depth, Rows{1, 0, 1, H}, OutDesc{fb_device, fb_format, 1, 0, W}, tiles, ntiles};
+  const int rc = validate(c, q, tiles, ntiles);
+  return rc != RT_OK ? rc : enqueue(c, q);
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {
   if (!c || !n_out || max_n < 0 || (max_n > 0 && !ms_out)) return RT_ERR_INVALID_ARG;
   RT_TRY(c, hipSetDevice(c->device));
   RT_TRY(c, hipStreamSynchronize(c->stream));
-  long long avail = c->launches - c->hist_begin;
-  if (avail > rt_ctx::kRing) avail = rt_ctx::kRing;
+  long long avail = c->timing.launches - c->timing.hist_begin;
+  if (avail > LaunchTiming::kRing) avail = LaunchTiming::kRing;
   if (avail > max_n) avail = max_n;
   for (long long i = 0; i < avail; i++) {
-    const int slot = (int)((c->launches - avail + i) % rt_ctx::kRing);
+    const int slot = (int)((c->timing.launches - avail + i) % LaunchTiming::kRing);
     float ms = 0.f;
-    RT_TRY(c, hipEventElapsedTime(&ms, c->ev0[slot], c->ev1[slot]));
+    RT_TRY(c, hipEventElapsedTime(&ms, c->timing.ev0[slot], c->timing.ev1[slot]));
     ms_out[i] = ms;
   }
   *n_out = (int)avail;
-  c->hist_begin = c->launches;
+  c->timing.hist_begin = c->timing.launches;
   return RT_OK;
 }
 
 int rt_get_info(rt_ctx *c, rt_info *out) {
   if (!c || !out) return RT_ERR_INVALID_ARG;
   *out = rt_info{};
-  out->cam_grid_last = c->cg_last ? 1 : 0;
-  out->cam_grid_n = c->cg_last_n;
-  out->cam_grid_builds = c->cg_builds;
-  out->cam_grid_build_ms = c->cg_build_ms;
-  out->tile_order_builds = c->perm_builds;
-  out->tile_order_build_ms = c->perm_build_ms;
-  out->upload_ms = c->upload_ms;
-  out->launches = (uint64_t)c->launches;
+  out->cam_grid_last = c->info.cg_last ? 1 : 0;
+  out->cam_grid_n = c->info.cg_last_n;
+  out->cam_grid_builds = c->info.cg_builds;
+  out->cam_grid_build_ms = c->info.cg_build_ms;
+  out->tile_order_builds = c->info.perm_builds;
+  out->tile_order_build_ms = c->info.perm_build_ms;
+  out->upload_ms = c->info.upload_ms;
+  out->launches = (uint64_t)c->timing.launches;
   const Scene &scn = c->scene;
   out->sphere_grids = scn.sg_ok ? scn.sg_grids : 0;
   out->sphere_grid_n = scn.sg_ok ? scn.sg_n : 0;
   out->sphere_grid_entries = scn.sg_ok ? (uint64_t)scn.sg_entries : 0;
-  out->sphere_grid_build_ms = c->sg_build_ms;
+  out->sphere_grid_build_ms = c->info.sg_build_ms;
   out->behind_grid = scn.ug_ok ? 1 : 0;
-  out->behind_grid_last = c->ug_last ? 1 : 0;
+  out->behind_grid_last = c->info.ug_last ? 1 : 0;
   out->behind_grid_cells = scn.ug_ok ? (uint64_t)scn.ug.nx * (uint64_t)scn.ug.ny * (uint64_t)scn.ug.nz : 0;
   out->behind_grid_entries = scn.ug_ok ? (uint64_t)scn.ug_entries : 0;
-  out->behind_grid_build_ms = c->ug_build_ms;
-  out->bvh_build_ms = c->bvh_build_ms;
-  out->light_grid_build_ms = c->lg_build_ms;
+  out->behind_grid_build_ms = c->info.ug_build_ms;
+  out->bvh_build_ms = c->info.bvh_build_ms;
+  out->light_grid_build_ms = c->info.lg_build_ms;
   out->scratch_bytes = (uint64_t)(c->gstack.bytes() + c->dq.bytes() + c->homes.bytes() + c->home_bits.bytes() +
-                                  c->cg_bytes() + c->perm.bytes());
-  out->shadow_line_bounded = c->lg_off_free ? 1 : 0;
+                                  c->cg.bytes() + c->order.perm.bytes());
+  out->shadow_line_bounded = c->scene.lg_off_free ? 1 : 0;
   out->reserved0 = 0;
   return RT_OK;
 }
