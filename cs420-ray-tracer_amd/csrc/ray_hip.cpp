@@ -16,6 +16,9 @@
 // G devices in cyclic 8-row bands, gathered to device 0 with ncclGather over
 // xGMI), --device N, --out FILE, --p6 (binary PPM), --repeat N, --json, and
 // -a (4-sample antialias, the ray_cuda flag of src/main_gpu.cu:363-370).
+// --devices LIST (e.g. 0,1,2 or 0,0,0): the same row shards, one per listed
+// device, through the library's device group (rt_group_*, no RCCL); a device
+// may repeat, so one GPU can rehearse the multi-device path.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -44,12 +47,15 @@ struct Opts {
   bool p6 = false, json = false;
   bool force_gather = false;  // --force-gather: the G-device gather path even for G = 1 (rehearsal)
   int samples = 1;
+  std::vector<int> devices;  // --devices LIST: the pass renders through rt_group_*
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
-               "          [--out FILE] [--p6] [--repeat N] [--json] [scene.txt]\n",
+               "          [--devices D0,D1,...] [--out FILE] [--p6] [--repeat N] [--json] [scene.txt]\n"
+               "  --devices LIST  one row shard per listed device through the library's device group\n"
+               "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n",
                argv0);
   return 2;
 }
@@ -182,6 +188,48 @@ int render_multi(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_
   return 0;
 }
 
+// --devices: one shard per listed device through the library's device group.
+int render_group(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
+  rt_group *grp = nullptr;
+  CK(rt_group_create(o.devices.data(), (int)o.devices.size(), 8, &grp));
+  auto run = [&]() -> int {
+    int rc = rt_group_upload_scene(grp, &sc);
+    if (rc == RT_OK) rc = rt_group_set_antialias(grp, o.samples);
+    rt_stats st{};
+    for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
+      auto t0 = std::chrono::high_resolution_clock::now();
+      rc = rt_group_render(grp, &cam, o.width, o.height, o.depth, img, 0, &st);
+      auto t1 = std::chrono::high_resolution_clock::now();
+      res.wall_s = std::chrono::duration<double>(t1 - t0).count();
+    }
+    res.kernel_ms = st.kernel_ms;
+    res.primary = st.rays_primary;
+    res.shadow = st.rays_shadow;
+    res.reflect = st.rays_reflect;
+    res.negative = st.negative_clamped;
+    return rc;
+  };
+  const int rc = run();
+  if (rc != RT_OK)
+    std::fprintf(stderr, "device group failed: %s (%s)\n", rt_error_string(rc), rt_group_last_error(grp));
+  rt_group_destroy(grp);
+  return rc != RT_OK ? 1 : 0;
+}
+
+// "0,1,2" -> {0, 1, 2}; false unless every item is a non-negative decimal number.
+bool parse_devices(const char *list, std::vector<int> &out) {
+  out.clear();
+  for (const char *p = list;; p++) {
+    if (*p < '0' || *p > '9') return false;
+    long v = 0;
+    for (; *p >= '0' && *p <= '9'; p++)
+      if ((v = v * 10 + (*p - '0')) > 1 << 20) return false;
+    out.push_back((int)v);
+    if (*p == '\0') return true;
+    if (*p != ',') return false;
+  }
+}
+
 int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const char *label, const char *file) {
   // the image: 2 MB-aligned and advised for huge pages (3 page faults at
   // 1080p instead of ~1,500), zeroed here as the reference value-initialises
@@ -198,7 +246,9 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
   (void)madvise(img.get(), img_cap, MADV_HUGEPAGE);
   std::memset(img.get(), 0, img_cap);
   Result res;
-  int rc = (o.gpus > 1 || o.force_gather) ? render_multi(o, sc, cam, img.get(), res) : render_single(o, sc, cam, img.get(), res);
+  int rc = !o.devices.empty()               ? render_group(o, sc, cam, img.get(), res)
+           : (o.gpus > 1 || o.force_gather) ? render_multi(o, sc, cam, img.get(), res)
+                                            : render_single(o, sc, cam, img.get(), res);
   if (rc) return rc;
   if (o.mode == "hip")
     std::printf("GPU rendering time: %g seconds\n", res.wall_s);  // main_gpu.cu:519
@@ -213,7 +263,8 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
         "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"depth\": %d, \"gpus\": %d, \"rays\": %llu, "
         "\"primary\": %llu, \"shadow\": %llu, \"reflect\": %llu, \"kernel_ms\": %.4f, \"wall_ms\": %.4f, "
         "\"mrays_per_s\": %.2f}\n",
-        o.scene.c_str(), o.width, o.height, o.depth, o.gpus, (unsigned long long)rays,
+        o.scene.c_str(), o.width, o.height, o.depth, o.devices.empty() ? o.gpus : (int)o.devices.size(),
+        (unsigned long long)rays,
         (unsigned long long)res.primary, (unsigned long long)res.shadow, (unsigned long long)res.reflect,
         res.kernel_ms, res.wall_s * 1e3, rays / (res.kernel_ms * 1e-3) / 1e6);
   }
@@ -248,6 +299,7 @@ int main(int argc, char **argv) {
     else if (a == "--depth") { if (!next(o.depth)) return usage(argv[0]); }
     else if (a == "--gpus") { if (!next(o.gpus)) return usage(argv[0]); }
     else if (a == "--device") { if (!next(o.device)) return usage(argv[0]); }
+    else if (a == "--devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.devices)) return usage(argv[0]); }
     else if (a == "--repeat") { if (!next(o.repeat)) return usage(argv[0]); }
     else if (a == "--out") { if (i + 1 >= argc) return usage(argv[0]); o.out = argv[++i]; }
     else if (a == "--p6") o.p6 = true;
@@ -258,6 +310,7 @@ int main(int argc, char **argv) {
     else o.scene = a;  // any other argument is the scene path, as main.cpp:103-110
   }
   if (o.width <= 0 || o.height <= 0 || o.gpus < 1 || o.repeat < 1) return usage(argv[0]);
+  if (!o.devices.empty() && (o.gpus > 1 || o.force_gather)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116
   rt_scene sc;

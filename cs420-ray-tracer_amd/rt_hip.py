@@ -130,6 +130,15 @@ SIGNATURES = {
                                   C.c_int, _P]),
     "rt_set_antialias": (C.c_int, [_P, C.c_int]),
     "rt_get_info": (C.c_int, [_P, C.POINTER(rt_info)]),
+    "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
+    "rt_group_destroy": (None, [_P]),
+    "rt_group_size": (C.c_int, [_P]),
+    "rt_group_member": (_P, [_P, C.c_int]),
+    "rt_group_last_error": (C.c_char_p, [_P]),
+    "rt_group_upload_scene": (C.c_int, [_P, C.POINTER(rt_scene)]),
+    "rt_group_set_antialias": (C.c_int, [_P, C.c_int]),
+    "rt_group_render": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, _P, C.c_int,
+                                  C.POINTER(rt_stats)]),
 }
 
 # include/rt_hip_compat.h: the reference's hybrid interface (src/kernel.cu:185-207),
@@ -393,6 +402,75 @@ class Renderer:
         if self._ctx:
             self._L.rt_destroy(self._ctx)
             self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Group:
+    """A device group (rt_group): one image rendered as len(devices) cyclic row
+    shards of `band` rows, one per member, assembled on devices[0].  A device
+    may repeat ([0, 0, 0] is three shards on one GPU).  What ray_hip --gpus does
+    with RCCL (render_multi, csrc/ray_hip.cpp), as one library call."""
+
+    def __init__(self, devices, band: int = 8, variant: str | None = None):
+        """variant: None = the product library; "tuning" / "check" = a test build (VARIANTS)."""
+        self._L = variant_lib(variant)
+        self.variant = variant
+        self._grp = C.c_void_p()
+        self.devices = [int(d) for d in devices]
+        self.band = band
+        arr = (C.c_int * max(1, len(self.devices)))(*self.devices)
+        _check(self._L.rt_group_create(arr, len(self.devices), band, C.byref(self._grp)),
+               f"rt_group_create({self.devices}, band={band})", L=self._L)
+
+    def _check_grp(self, rc: int, what: str):
+        if rc != 0:
+            raise RtError(rc, what, self._L.rt_group_last_error(self._grp).decode())
+
+    @property
+    def size(self) -> int:
+        return self._L.rt_group_size(self._grp)
+
+    def upload(self, scene: Scene):
+        self._check_grp(self._L.rt_group_upload_scene(self._grp, C.byref(scene.raw)), "rt_group_upload_scene")
+
+    def set_antialias(self, samples: int):
+        self._check_grp(self._L.rt_group_set_antialias(self._grp, samples), "rt_group_set_antialias")
+
+    def render(self, cam: rt_camera, width: int, height: int, depth: int, out=None,
+               out_on_device: bool = False) -> tuple[object, rt_stats]:
+        """Render the whole image into `out` (a host bytearray if None; with
+        out_on_device a buffer of devices[0]) and return (buffer, stats): the ray
+        counts summed over the members, kernel_ms their maximum."""
+        if out is None:
+            out = bytearray(height * width * 3)
+        st = rt_stats()
+        self._check_grp(self._L.rt_group_render(self._grp, C.byref(cam), width, height, depth, C.c_void_p(_addr(out)),
+                                            int(out_on_device), C.byref(st)), "rt_group_render")
+        return out, st
+
+    def member(self, i: int):
+        """The borrowed rt_ctx of member i (rt_group_member)."""
+        ctx = self._L.rt_group_member(self._grp, i)
+        if not ctx:
+            raise IndexError(f"group member {i} of {self.size}")
+        return C.c_void_p(ctx)
+
+    def member_stats(self, i: int) -> rt_stats:
+        """rt_render_stats of member i: its shard of the most recent render."""
+        ctx = self.member(i)
+        st = rt_stats()
+        _check(self._L.rt_render_stats(ctx, C.byref(st)), f"rt_render_stats(member {i})", ctx, L=self._L)
+        return st
+
+    def close(self):
+        if self._grp:
+            self._L.rt_group_destroy(self._grp)
+            self._grp = C.c_void_p()
 
     def __del__(self):
         try:

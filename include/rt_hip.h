@@ -20,6 +20,10 @@
  *   rt_write_ppm                    <- write_ppm()            src/main.cpp:69-91
  *   rt_kernel_times                 <- cudaEventElapsedTime around the kernel, src/main_gpu.cu:496-519
  *   rt_unpermute_rows               <- (new) reassembly of the multi-GPU row shards
+ *   rt_group_create / _destroy / _size / _member / _last_error / _upload_scene / _set_antialias / _render
+ *                                   <- (new) render_multi in csrc/ray_hip.cpp: the contexts, streams
+ *                                      and shard buffers of G devices, the gather to device 0 and the reassembly,
+ *                                      as one library call without RCCL
  *   rt_render_tiles                 <- the same for a list of tiles in one launch (the hybrid driver's GPU share)
  *   rt_render_tile                  <- launch_gpu_kernel's tile semantics  src/kernel.cu:185-200 (x = tile_x + ...,
  *                                      y = tile_y + ..., fb[y*W + x], kernel.cu:99-112), as main_hybrid.cpp:457-470
@@ -56,7 +60,8 @@ extern "C" {
                                    6: rt_render_tiles; 7: rt_get_info; 8: rt_info sphere-grid fields;
                                    9: rt_info behind-grid fields; 10: RT_ERR_CHECK;
                                    11: rt_info BVH / light-grid build times, scratch bytes;
-                                   12: rt_info shadow_line_bounded */
+                                   12: rt_info shadow_line_bounded; the rt_group_* entry points were added
+                                   under 12 as well (new symbols only: nothing existing changed) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -302,6 +307,34 @@ int rt_get_info(rt_ctx *ctx, rt_info *out);
  * [H][W][3] image.  Both pointers are device memory; runs on the ctx stream. */
 int rt_unpermute_rows(rt_ctx *ctx, const uint8_t *gathered_device, uint8_t *image_device, int width, int height,
                       int band, int num_shards, int rows_per_shard);
+
+/* ---- device group: one image row-sharded over several contexts ------------
+ * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
+ * streams and shard buffers, ncclGather to device 0, rt_unpermute_rows -- with
+ * one call that needs no RCCL: shards travel with hipMemcpyPeerAsync and are
+ * placed into the image as they arrive.  Every rt_group_* call returns an
+ * rt_status; argument errors return before any HIP call. */
+typedef struct rt_group rt_group;
+/* n >= 1 members; devices[i] may repeat (several shards on one device). band >= 1 is the cyclic band height
+   (the CLI uses 8). Member i renders rt_rows_for_shard(H, band, i, n). The image is assembled on devices[0].
+   Replaces render_multi's set-up (ray_hip.cpp): rt_create per device, streams, ncclCommInitAll.  On failure
+   every member already created is destroyed and *out stays NULL. */
+int  rt_group_create(const int *devices, int n, int band, rt_group **out);
+/* Replaces render_multi's tear-down.  NULL is allowed. */
+void rt_group_destroy(rt_group *grp);
+int  rt_group_size(const rt_group *grp);               /* members (0 for NULL) */
+rt_ctx *rt_group_member(rt_group *grp, int index);     /* borrowed; for rt_get_info / rt_render_stats / rt_kernel_times;
+                                                          NULL outside [0, size).  Its stream is the group's. */
+const char *rt_group_last_error(const rt_group *grp);
+/* rt_upload_scene / rt_set_antialias on every member (render_multi's per-device loop). */
+int  rt_group_upload_scene(rt_group *grp, const rt_scene *scene);
+int  rt_group_set_antialias(rt_group *grp, int samples);
+/* Synchronous. rgb_out: H*W*3 bytes in PPM row order, host memory or (out_on_device=1) memory of devices[0].
+   stats (nullable): ray counts summed over members, kernel_ms = max over members.
+   Replaces render_multi's frame: rt_render_async per shard, ncclGather, rt_unpermute_rows.  The image is
+   assembled on a blocking stream of devices[0] (ordered with the legacy NULL stream, as a context's own). */
+int  rt_group_render(rt_group *grp, const rt_camera *cam, int width, int height, int depth,
+                     uint8_t *rgb_out, int out_on_device, rt_stats *stats);
 
 #ifdef __cplusplus
 }
