@@ -178,20 +178,28 @@ __device__ __forceinline__ D3 normalized(D3 a) {
 // division for 500 M numerators over the exponent range and at binade edges
 // and for random, reflected and perturbed vectors (tests/native/renorm_check.cpp).
 // Any other length, a tiny component or a NaN takes normalized().
-__device__ __forceinline__ D3 renormalized(D3 a) {
-  constexpr double u = 0x1p-53;
+// The two halves are separate so that a caller can ask a whole wave for the
+// fast path first (renorm_near_one) and then run it with no fall-back compiled
+// in (renorm_near_one_quot): renormalized() is the per-lane composition.
+__device__ __forceinline__ bool renorm_near_one(D3 a, double &t) {
   const double s = (a.x * a.x + a.y * a.y) + a.z * a.z;
-  const double t = (s - 1.0) * 0x1p53;
+  t = (s - 1.0) * 0x1p53;
   auto usable = [](double x) { return __builtin_fabs(x) >= 0x1p-959 || x == 0.0; };
-  if (__builtin_expect(t >= -4.0 && t <= 6.0 && usable(a.x) && usable(a.y) && usable(a.z), 1)) {
-    const double len = t > 3.0 ? 1.0 + 2.0 * u : (t > -0.5 ? 1.0 : (t > -2.5 ? 1.0 - u : 1.0 - 2.0 * u));
-    const double rcp = t > 3.0 ? 1.0 - 2.0 * u : (t > -0.5 ? 1.0 : 1.0 + 2.0 * u);
-    auto q = [&](double x) {
-      const double q0 = x * rcp;
-      return __builtin_copysign(__builtin_fma(__builtin_fma(-q0, len, x), rcp, q0), x);
-    };
-    return mk(q(a.x), q(a.y), q(a.z));
-  }
+  return t >= -4.0 && t <= 6.0 && usable(a.x) && usable(a.y) && usable(a.z);
+}
+__device__ __forceinline__ D3 renorm_near_one_quot(D3 a, double t) {
+  constexpr double u = 0x1p-53;
+  const double len = t > 3.0 ? 1.0 + 2.0 * u : (t > -0.5 ? 1.0 : (t > -2.5 ? 1.0 - u : 1.0 - 2.0 * u));
+  const double rcp = t > 3.0 ? 1.0 - 2.0 * u : (t > -0.5 ? 1.0 : 1.0 + 2.0 * u);
+  auto q = [&](double x) {
+    const double q0 = x * rcp;
+    return __builtin_copysign(__builtin_fma(__builtin_fma(-q0, len, x), rcp, q0), x);
+  };
+  return mk(q(a.x), q(a.y), q(a.z));
+}
+__device__ __forceinline__ D3 renormalized(D3 a) {
+  double t;
+  if (__builtin_expect(renorm_near_one(a, t), 1)) return renorm_near_one_quot(a, t);
   return normalized(a);
 }
 
@@ -1525,7 +1533,29 @@ __device__ __forceinline__ int lg_first(const LgArgs &lg, LgRange r) {
   return (r.cb >= 0 && r.ce > r.cb) ? lg.ids[RT_CK(kCkLgId, r.cb, lg.nids)] : 0;
 }
 
+// The guards of one light's shadow query that almost every lane passes, as
+// one lane predicate formed from what the light's setup computes anyway: the
+// direction takes renormalized()'s near-one path (`t`: its argument for
+// renorm_near_one_quot), shadow_cells' `fast` holds, the cell is binnable, and
+// the host has bounded every line's distance from its light (off_free).  Of
+// `fast` only the distance is tested: a direction from renorm_near_one_quot
+// has components RN(x / len) with |len - 1| <= 2u and |x|^2 within 6u of 1, so
+// a = dot(d, d) is within 2^-48 of 1 and a2_ok(2a) holds; dist >= 2^-900 is
+// false for a NaN and is T >= 2^-900 (T = min(dist, kInf)).  A wave whose
+// active lanes all hold it runs shadow_cells<true>.
+__device__ __forceinline__ bool light_common(const LgArgs &lg, LgRange cell, double dist, D3 ldir, double &t) {
+  return renorm_near_one(ldir, t) && lg.off_free && cell.cb >= 0 && dist >= 0x1p-900;
+}
+
 // `pre` >= 0: the sphere the shaded point lies on (see below).
+// kCommon: the straight-line form, for a wave whose active lanes all hold
+// light_common() for this light.  The guards that predicate stands for are
+// compiled out (`fast`, the `all` selects of the list loop, the line check,
+// `pre` >= 0); what is left is the same operations on the same operands in the
+// same order, so a lane's result is the one the general form gives it.  The
+// exact test's tiny-numerator case (intersect_num's 2) depends on the sphere,
+// not on the light, and stays, as the loop's one cold region.
+template <bool kCommon = false>
 __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n, bool act, D3 o, D3 d, D3 lp,
                                              double dist, const LgArgs &lg, int l, LgRange cell, int id0,
                                              Work &work, int pre = -1) {
@@ -1533,7 +1563,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
   const double a = dot(d, d);
   const double a4 = 4.0 * a, a2 = 2.0 * a;
   const double T = dist < kInf ? dist : kInf;
-  const bool fast = a2_ok(a2) && dist == dist && T >= 0x1p-900;
+  const bool fast = kCommon || (a2_ok(a2) && dist == dist && T >= 0x1p-900);
   const double q = a2 * T, qlo = q * (1.0 - 0x1p-48), qhi = q * (1.0 + 0x1p-48);
   bool occ = false;
   auto test = [&](int i) {
@@ -1547,7 +1577,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
         const double t = num / a2;
         occ = t < kInf && t < dist;
       }
-    } else if (r == 2) {
+    } else if (__builtin_expect(r == 2, 0)) {
       double t;
       occ = intersect(g[i], o, d, a4, a2, t) && t < kInf && t < dist;
     }
@@ -1570,7 +1600,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
   //    then skip that sphere.  disc == 0 (the negative tangent root the
   //    reference keeps, sphere.h:43-47) and every other case take the test.
   bool self_miss = false;
-  if (act && pre >= 0 && fast) {
+  if (act && (kCommon || pre >= 0) && fast) {
     const SphGeo s = g[RT_CK(kCkSphere, pre, n)];
     const double ocx = o.x - s.cx, ocy = o.y - s.cy, ocz = o.z - s.cz;
     const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.rr;
@@ -1593,7 +1623,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
     // is below 60 u (4B + 2 EPSILON) + the cross product's rounding, far
     // under 2^-41 (1.01 B + 0.01) <= max_off; tests/native/num_check.cpp)
     bool off_ok = true;
-    if (!lg.off_free) {
+    if (!kCommon && !lg.off_free) {
       const D3 w = sub(lp, o);
       const double off = __builtin_fabs(w.y * d.z - w.z * d.y) + __builtin_fabs(w.z * d.x - w.x * d.z) +
                          __builtin_fabs(w.x * d.y - w.y * d.x);
@@ -1602,7 +1632,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
     // the cell's list (first id prefetched), then the global list; a lane
     // whose line cannot use the grid tests every sphere (ids 0 .. n-1) in the
     // same loop
-    const bool all = !off_ok || cell.cb < 0;
+    const bool all = !kCommon && (!off_ok || cell.cb < 0);
     const int cl = RT_CK(kCkLgStart, cells, lg.nstart - 1 - (long long)l * (cells + 2));
     const int gb = st[cl], ge = st[cl + 1];
     const int len1 = all ? n : cell.ce - cell.cb, len = all ? n : len1 + (ge - gb);

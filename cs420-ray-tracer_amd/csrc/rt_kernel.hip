@@ -183,7 +183,13 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, int k) {
 // loop below (the hit lane's normal and view direction passed over) -- and each
 // hit lane then adds its lights' terms in file order (scene.h:117): the same
 // bits, in ceil(lights / lpp) passes instead of one per light.
-template <bool kCull, bool kArgMem = false, bool kFast = false, bool kWide = false>
+// kTwoForms (kFast, the lane-per-ray loop): each light's shadow query has a
+// straight-line form for the waves whose lanes all pass the light's guards
+// (rt_device.h light_common, shadow_cells<true>) beside the general one.  The
+// render kernel has it (synth200 0.186 -> 0.181 ms per frame); the deferred
+// kernels and the wide loop do not: there it measured no faster, and in the
+// wide loop it costs 16 more VGPR spills.
+template <bool kCull, bool kArgMem = false, bool kFast = false, bool kWide = false, bool kTwoForms = true>
 __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const double *__restrict__ rad,
                                           const SphMat *__restrict__ mat, const LightD *__restrict__ slight, int n,
                                           int nl, D3 amb, const BvhArgs &bv, const LgArgs &lg_arg, bool alive, D3 o,
@@ -299,14 +305,25 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
         RT_T0(t_sh);
         bool occ = false;
         if (__ballot(need)) {
-          const D3 so = add(hp, scale(ldir, kEps)), sd = renormalized(ldir);
-          if constexpr (kFast) {
-            occ = shadow_cells(g, n, need, so, sd, lp, dist, lg, l, cell, id0, work, hi);
-          }
-          else
+          const D3 so = add(hp, scale(ldir, kEps));
+          if constexpr (kFast && kTwoForms) {
+            // a wave with no rare lane for this light (light_common) takes the
+            // query's straight-line form; any other wave the general one
+            double rt;
+            const bool common = light_common(lg, cell, dist, ldir, rt);
+            if (__ballot(need && !common) == 0)
+              occ = shadow_cells<true>(g, n, need, so, renorm_near_one_quot(ldir, rt), lp, dist, lg, l, cell, id0,
+                                       work, hi);
+            else
+              occ = shadow_cells(g, n, need, so, renormalized(ldir), lp, dist, lg, l, cell, id0, work, hi);
+          } else if constexpr (kFast) {
+            occ = shadow_cells(g, n, need, so, renormalized(ldir), lp, dist, lg, l, cell, id0, work, hi);
+          } else {
+            const D3 sd = renormalized(ldir);
             occ = lg.on ? shadow_cells(g, n, need, so, sd, lp, dist, lg, l, cell, id0, work, hi)
                         : sweep_shadow<kCull>(g, rad, n, need, so, sd, lp, hi, dist,
                                               kernarg_late<kArgMem, offsetof(RenderArgs, bv)>(bv), work);
+          }
         }
         RT_ACC(work, 9, t_sh);
         RT_T0(t_shade);
@@ -397,7 +414,7 @@ __device__ __forceinline__ int closest_hit(const SphGeo *__restrict__ g, const d
   return bi;
 }
 
-template <bool kCull, bool kArgMem = false, bool kFast = false, bool kWide = false>
+template <bool kCull, bool kArgMem = false, bool kFast = false, bool kWide = false, bool kTwoForms = true>
 __device__ __forceinline__ void bounce(const SphGeo *__restrict__ g, const double *__restrict__ rad,
                                        const SphMat *__restrict__ mat, const LightD *__restrict__ slight, int n,
                                        int nl, D3 amb, const BvhArgs &bv, const LgArgs &lg_arg, bool alive, D3 o, D3 d,
@@ -405,7 +422,7 @@ __device__ __forceinline__ void bounce(const SphGeo *__restrict__ g, const doubl
                                        double &refl, D3 &no, D3 &nd, int &nkey, bool cam_pass = false) {
   double bt;
   const int bi = closest_hit<kCull, kArgMem, kFast>(g, rad, n, bv, alive, o, d, key, work, bt, cam_pass);
-  shade_hit<kCull, kArgMem, kFast, kWide>(g, rad, mat, slight, n, nl, amb, bv, lg_arg, alive, o, d, key, dleft, bi, bt,
+  shade_hit<kCull, kArgMem, kFast, kWide, kTwoForms>(g, rad, mat, slight, n, nl, amb, bv, lg_arg, alive, o, d, key, dleft, bi, bt,
                                           work, c_shadow, outcome, color, refl, no, nd, nkey);
 }
 
@@ -1216,7 +1233,7 @@ __global__ __launch_bounds__(64, RT_MIN_WAVES_PER_EU) void render_deferred(const
       int outcome = 0, nkey = 0;
       D3 color = mk(0.0, 0.0, 0.0), no = o, nd = d;
       double refl = 0.0;
-      bounce<kCull, true, kFast, kWide>(a.geo, a.radius, a.mat, a.lights, a.n, a.nl, a.amb, a.bv, a.lg, act, o, d, key,
+      bounce<kCull, true, kFast, kWide, false>(a.geo, a.radius, a.mat, a.lights, a.n, a.nl, a.amb, a.bv, a.lg, act, o, d, key,
                                         dleft, work, c_shadow, outcome, color, refl, no, nd, nkey);
       if (act) {
         StackEnt *gs = kernarg_late<true, offsetof(RenderArgs, dstack)>(a.dstack);
@@ -1355,7 +1372,7 @@ __global__ __launch_bounds__(64, RT_MIN_WAVES_PER_EU) void render_deferred_walk(
       int outcome = 0, nkey = 0;
       D3 color = mk(0.0, 0.0, 0.0), no = o, nd = d;
       double refl = 0.0;
-      shade_hit<true, true, true>(a.geo, a.radius, a.mat, a.lights, a.n, a.nl, a.amb, a.bv, a.lg, ready, o, d, key,
+      shade_hit<true, true, true, false, false>(a.geo, a.radius, a.mat, a.lights, a.n, a.nl, a.amb, a.bv, a.lg, ready, o, d, key,
                                    dleft, bi, bt, work, c_shadow, outcome, color, refl, no, nd, nkey);
       bool spawned = false;
       if (ready) {
