@@ -19,6 +19,11 @@
 // --devices LIST (e.g. 0,1,2 or 0,0,0): the same row shards, one per listed
 // device, through the library's device group (rt_group_*, no RCCL); a device
 // may repeat, so one GPU can rehearse the multi-device path.
+// --frames N [--batch B] (only with --devices): every pass renders a sequence
+// of N frames of the scene's view with rt_group_render_frames, the members in
+// launches of at most B frames (default: the library's largest), into memory of
+// the first device; the time line is the whole sequence's, one more line gives
+// the frames and the time per frame, and the LAST frame is the output image.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -48,15 +53,19 @@ struct Opts {
   bool force_gather = false;  // --force-gather: the G-device gather path even for G = 1 (rehearsal)
   int samples = 1;
   std::vector<int> devices;  // --devices LIST: the pass renders through rt_group_*
+  int frames = -1, batch = -1;  // --frames N [--batch B]: a sequence per pass (rt_group_render_frames); -1: not given
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
-               "          [--devices D0,D1,...] [--out FILE] [--p6] [--repeat N] [--json] [scene.txt]\n"
+               "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
+               "          [--json] [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
-               "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n",
-               argv0);
+               "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
+               "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
+               "                  sequence and writes the last; --batch B (0..%d, 0 = %d): frames per launch\n",
+               argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
   return 2;
 }
 
@@ -89,6 +98,7 @@ struct Result {
   double wall_s = 0;       // host wall time of the last frame (render + gather)
   double kernel_ms = 0;    // max over devices of the render kernel time
   uint64_t primary = 0, shadow = 0, reflect = 0, negative = 0;
+  int frames = 0;          // --frames: wall_s, kernel_ms and the counts are the sequence's
 };
 
 // Single device: render the full frame.
@@ -191,16 +201,37 @@ int render_multi(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_
 // --devices: one shard per listed device through the library's device group.
 int render_group(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
   rt_group *grp = nullptr;
+  uint8_t *seq = nullptr;
   CK(rt_group_create(o.devices.data(), (int)o.devices.size(), 8, &grp));
   auto run = [&]() -> int {
     int rc = rt_group_upload_scene(grp, &sc);
     if (rc == RT_OK) rc = rt_group_set_antialias(grp, o.samples);
     rt_stats st{};
-    for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
+    // --frames: the sequence stays in memory of the first device, the last frame is copied out
+    const size_t image_bytes = (size_t)o.width * o.height * 3;
+    const std::vector<rt_camera> cams(o.frames > 0 ? (size_t)o.frames : 0, cam);
+    hipError_t he = hipSuccess;
+    if (o.frames > 0 && rc == RT_OK) {
+      he = hipSetDevice(o.devices[0]);
+      if (he == hipSuccess) he = hipMalloc(&seq, image_bytes * cams.size());
+    }
+    for (int it = 0; it < o.repeat && rc == RT_OK && he == hipSuccess; it++) {
       auto t0 = std::chrono::high_resolution_clock::now();
-      rc = rt_group_render(grp, &cam, o.width, o.height, o.depth, img, 0, &st);
+      rc = o.frames > 0 ? rt_group_render_frames(grp, cams.data(), o.frames, o.width, o.height, o.depth,
+                                                 o.batch < 0 ? 0 : o.batch, seq, 1, image_bytes, &st)
+                        : rt_group_render(grp, &cam, o.width, o.height, o.depth, img, 0, &st);
       auto t1 = std::chrono::high_resolution_clock::now();
       res.wall_s = std::chrono::duration<double>(t1 - t0).count();
+    }
+    if (o.frames > 0 && rc == RT_OK && he == hipSuccess) {
+      he = hipSetDevice(o.devices[0]);
+      if (he == hipSuccess)
+        he = hipMemcpy(img, seq + image_bytes * (cams.size() - 1), image_bytes, hipMemcpyDeviceToHost);
+      res.frames = o.frames;
+    }
+    if (he != hipSuccess) {
+      std::fprintf(stderr, "the sequence's buffer on device %d: %s\n", o.devices[0], hipGetErrorString(he));
+      return RT_ERR_HIP;
     }
     res.kernel_ms = st.kernel_ms;
     res.primary = st.rays_primary;
@@ -212,6 +243,7 @@ int render_group(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_
   const int rc = run();
   if (rc != RT_OK)
     std::fprintf(stderr, "device group failed: %s (%s)\n", rt_error_string(rc), rt_group_last_error(grp));
+  if (seq) (void)hipFree(seq);
   rt_group_destroy(grp);
   return rc != RT_OK ? 1 : 0;
 }
@@ -254,17 +286,20 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
     std::printf("GPU rendering time: %g seconds\n", res.wall_s);  // main_gpu.cu:519
   else
     std::printf("%s time: %g seconds\n", label, res.wall_s);      // main.cpp:161 / :203
+  if (res.frames)
+    std::printf("Frames: %d, %g ms per frame\n", res.frames, res.wall_s * 1e3 / res.frames);
   if (res.negative)
     std::fprintf(stderr, "warning: %llu channels quantised below 0 were stored as 0\n",
                  (unsigned long long)res.negative);
   if (o.json) {
     uint64_t rays = res.primary + res.shadow + res.reflect;
+    const std::string frames = res.frames ? "\"frames\": " + std::to_string(res.frames) + ", " : "";
     std::printf(
-        "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"depth\": %d, \"gpus\": %d, \"rays\": %llu, "
+        "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"depth\": %d, \"gpus\": %d, %s\"rays\": %llu, "
         "\"primary\": %llu, \"shadow\": %llu, \"reflect\": %llu, \"kernel_ms\": %.4f, \"wall_ms\": %.4f, "
         "\"mrays_per_s\": %.2f}\n",
         o.scene.c_str(), o.width, o.height, o.depth, o.devices.empty() ? o.gpus : (int)o.devices.size(),
-        (unsigned long long)rays,
+        frames.c_str(), (unsigned long long)rays,
         (unsigned long long)res.primary, (unsigned long long)res.shadow, (unsigned long long)res.reflect,
         res.kernel_ms, res.wall_s * 1e3, rays / (res.kernel_ms * 1e-3) / 1e6);
   }
@@ -300,6 +335,8 @@ int main(int argc, char **argv) {
     else if (a == "--gpus") { if (!next(o.gpus)) return usage(argv[0]); }
     else if (a == "--device") { if (!next(o.device)) return usage(argv[0]); }
     else if (a == "--devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.devices)) return usage(argv[0]); }
+    else if (a == "--frames") { if (!next(o.frames) || o.frames < 1) return usage(argv[0]); }
+    else if (a == "--batch") { if (!next(o.batch) || o.batch < 0 || o.batch > RT_MAX_FRAMES) return usage(argv[0]); }
     else if (a == "--repeat") { if (!next(o.repeat)) return usage(argv[0]); }
     else if (a == "--out") { if (i + 1 >= argc) return usage(argv[0]); o.out = argv[++i]; }
     else if (a == "--p6") o.p6 = true;
@@ -311,6 +348,7 @@ int main(int argc, char **argv) {
   }
   if (o.width <= 0 || o.height <= 0 || o.gpus < 1 || o.repeat < 1) return usage(argv[0]);
   if (!o.devices.empty() && (o.gpus > 1 || o.force_gather)) return usage(argv[0]);
+  if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116
   rt_scene sc;

@@ -27,6 +27,7 @@
 #include <string>
 
 #include "rt_hip.h"
+#include "rt_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -3720,3 +3721,39 @@ int rt_unpermute_rows(rt_ctx *c, const uint8_t *gathered, uint8_t *image, int W,
 }
 
 }  // extern "C"
+
+// ---- rt_internal.h: the device group's view of a member's launches ---------
+namespace {
+// acc[q] += counter q of one launch, summed over its shards.  One wave; only
+// the calling stream writes acc, so no atomics.
+__global__ __launch_bounds__(64) void add_counts_kernel(const unsigned long long *__restrict__ counters,
+                                                        unsigned long long *__restrict__ acc) {
+  const int q = threadIdx.x;
+  if (q >= kRtCountSlots) return;
+  unsigned long long s = 0ull;
+  for (int sh = 0; sh < kShards; sh++) s += counters[(size_t)sh * kShardStride + q];
+  acc[q] += s;
+}
+}  // namespace
+
+int rt_add_counts(rt_ctx *c, unsigned long long *acc) {
+  static_assert(kRtCountSlots == kCounters, "rt_stats' counters");
+  if (!c || !acc) return RT_ERR_INVALID_ARG;
+  RT_TRY(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(add_counts_kernel, dim3(1), dim3(64), 0, c->stream, c->ctr.cur, acc);
+  RT_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_launch_ms(rt_ctx *c, long long index, double *ms_out) {
+  if (!c || !ms_out || index < 0 || index >= c->timing.launches ||
+      c->timing.launches - index > LaunchTiming::kRing)
+    return RT_ERR_INVALID_ARG;
+  const int slot = (int)(index % LaunchTiming::kRing);
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipEventSynchronize(c->timing.ev1[slot]));
+  float ms = 0.f;
+  RT_TRY(c, hipEventElapsedTime(&ms, c->timing.ev0[slot], c->timing.ev1[slot]));
+  *ms_out = ms;
+  return RT_OK;
+}

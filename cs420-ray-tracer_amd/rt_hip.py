@@ -139,6 +139,8 @@ SIGNATURES = {
     "rt_group_set_antialias": (C.c_int, [_P, C.c_int]),
     "rt_group_render": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, _P, C.c_int,
                                   C.POINTER(rt_stats)]),
+    "rt_group_render_frames": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                         C.c_int, C.c_size_t, C.POINTER(rt_stats)]),
 }
 
 # include/rt_hip_compat.h: the reference's hybrid interface (src/kernel.cu:185-207),
@@ -451,6 +453,29 @@ class Group:
         st = rt_stats()
         self._check_grp(self._L.rt_group_render(self._grp, C.byref(cam), width, height, depth, C.c_void_p(_addr(out)),
                                             int(out_on_device), C.byref(st)), "rt_group_render")
+        return out, st
+
+    def render_frames(self, cams, width: int, height: int, depth: int, batch: int = 0, out=None,
+                      out_on_device: bool = False, frame_stride: int | None = None) -> tuple[object, rt_stats]:
+        """rt_group_render_frames: len(cams) frames (any number), frame f seen through
+        cams[f] and sharded as render() shards one, at `out` + f * frame_stride
+        (height * width * 3 if None; `out` a host bytearray if None, with
+        out_on_device a buffer of devices[0]).  The members render launches of at
+        most `batch` frames (0 = MAX_FRAMES) while the previous batch is assembled.
+        `cams` may be a ctypes array built beforehand (camera_array).  Returns
+        (buffer, stats): the ray counts summed over frames and members, kernel_ms
+        the largest member's sum over its launches."""
+        n = len(cams)
+        image = height * width * 3
+        if frame_stride is None:
+            frame_stride = image
+        if out is None:
+            out = bytearray(max(0, n - 1) * frame_stride + image)
+        arr = cams if isinstance(cams, C.Array) else camera_array(cams)
+        st = rt_stats()
+        self._check_grp(self._L.rt_group_render_frames(self._grp, arr, n, width, height, depth, batch,
+                                                       C.c_void_p(_addr(out)), int(out_on_device), frame_stride,
+                                                       C.byref(st)), "rt_group_render_frames")
         return out, st
 
     def member(self, i: int):

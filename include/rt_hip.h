@@ -24,6 +24,9 @@
  *                                   <- (new) render_multi in csrc/ray_hip.cpp: the contexts, streams
  *                                      and shard buffers of G devices, the gather to device 0 and the reassembly,
  *                                      as one library call without RCCL
+ *   rt_group_render_frames          <- (new) rt_frames.run_frames plus the RCCL gather of cs420-ray-tracer_amd/rt_frames.py:
+ *                                      a frame sequence on the group, batch b travelling to device 0 and being
+ *                                      reassembled while the members render batch b+1
  *   rt_render_tiles                 <- the same for a list of tiles in one launch (the hybrid driver's GPU share)
  *   rt_render_tile                  <- launch_gpu_kernel's tile semantics  src/kernel.cu:185-200 (x = tile_x + ...,
  *                                      y = tile_y + ..., fb[y*W + x], kernel.cu:99-112), as main_hybrid.cpp:457-470
@@ -61,7 +64,8 @@ extern "C" {
                                    9: rt_info behind-grid fields; 10: RT_ERR_CHECK;
                                    11: rt_info BVH / light-grid build times, scratch bytes;
                                    12: rt_info shadow_line_bounded; the rt_group_* entry points were added
-                                   under 12 as well (new symbols only: nothing existing changed) */
+                                   under 12 as well (new symbols only: nothing existing changed),
+                                   and so was rt_group_render_frames */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -335,6 +339,25 @@ int  rt_group_set_antialias(rt_group *grp, int samples);
    assembled on a blocking stream of devices[0] (ordered with the legacy NULL stream, as a context's own). */
 int  rt_group_render(rt_group *grp, const rt_camera *cam, int width, int height, int depth,
                      uint8_t *rgb_out, int out_on_device, rt_stats *stats);
+/* `nframes` (>= 1, not limited to RT_MAX_FRAMES) frames of the uploaded scene, frame f seen through
+   cams[f], each row-sharded over the members exactly as rt_group_render shards one frame, written to
+   rgb_out + f * frame_stride (H*W*3 bytes each, PPM row order; host memory, or memory of devices[0]
+   with out_on_device = 1): frame f is byte for byte what rt_group_render(grp, &cams[f], ...) writes, and
+   no byte between the frames (frame_stride > H*W*3) or outside them is written.  Members render in
+   launches of at most `batch` frames (1..RT_MAX_FRAMES; 0 = RT_MAX_FRAMES), split as
+   rt_frames.batch_sizes splits them (near-equal launches, larger first); a batch travels to devices[0]
+   and is assembled there while the members render the next one, and the host does not wait in between.
+   Synchronous: returns when every frame is in rgb_out.  RT_ERR_INVALID_ARG also for nframes > 1 with
+   frame_stride < H*W*3 (one frame ignores the stride, as rt_render_frames_async does).
+   stats (nullable): ray counts and negative_clamped summed over all frames and members;
+   kernel_ms = max over members of the sum of that member's launches.
+   Afterwards rt_render_stats on a borrowed member reports that member's LAST launch of the call (its
+   shard of the last batch), and rt_kernel_times every launch of the call, one per batch (the call itself
+   does not consume that history).
+   Replaces the frame loop of rt_frames.run_frames and its RCCL gather. */
+int  rt_group_render_frames(rt_group *grp, const rt_camera *cams, int nframes, int width, int height,
+                            int depth, int batch, uint8_t *rgb_out, int out_on_device,
+                            size_t frame_stride, rt_stats *stats);
 
 #ifdef __cplusplus
 }
