@@ -327,6 +327,107 @@ __host__ __device__ __forceinline__ int intersect_num(const SphGeo &s, D3 o, D3 
 }
 __host__ __device__ __forceinline__ bool a2_ok(double a2) { return a2 >= 0x1p-60 && a2 <= 0x1p60; }
 
+// "Some active lane of the wave holds x": the branches of the predicated
+// exact test below are taken by the whole wave or not at all.  On the host
+// (one lane) it is x itself, so the CPU checks run the same text
+// (tests/native/exact_forms_check.cpp).
+__host__ __device__ __forceinline__ bool any_lane(bool x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ballot(x) != 0;
+#else
+  return x;
+#endif
+}
+
+// intersect_num as lane predicates instead of per-lane early returns, for the
+// list loops, where the lanes of a wave test different spheres and the wave
+// runs the union of intersect_num's exec-mask regions for nearly every
+// candidate anyway.  The arithmetic is intersect_num's, operation for
+// operation; a lane's class is
+//   hit   -- intersect_num's 1, numerator `num`
+//   early -- its 3 (kShadow only: the bound is qocc)
+//   cold  -- its 2 (a tiny numerator), and every lane that is not `fast`
+//   none  -- a miss.
+// The square root is formed when some lane of the wave needs it; the lanes
+// that do not (a miss, a tangent, an early occluder) ignore its result.
+struct ExactNum {
+  double num;
+  bool hit, early, cold;
+};
+template <bool kShadow>
+__host__ __device__ __forceinline__ ExactNum exact_num(const SphGeo &s, D3 o, D3 d, double a4, bool fast,
+                                                       double qocc) {
+  const double ocx = o.x - s.cx, ocy = o.y - s.cy, ocz = o.z - s.cz;
+  const double b = 2.0 * ((ocx * d.x + ocy * d.y) + ocz * d.z);
+  const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.rr;
+  const double p = b * b;
+  const double disc = p - a4 * c;
+  const bool pos = fast & (disc > 0.0);  // a NaN disc: neither positive nor a tangent
+  const bool bpos = b > 0.0;
+  const bool negroots = bpos & (p > 1e-290) & (disc < p * (1.0 - 0x1p-50));
+  ExactNum r;
+  r.early = kShadow && (pos & !bpos & (c > 0.0) & (-b < qocc));
+  const bool need_sq = pos & !negroots & !r.early;
+  r.num = -b;
+  r.hit = fast & (disc == 0.0);
+  r.cold = !fast;
+  if (any_lane(need_sq)) {
+    const double sq = __builtin_sqrt(disc);
+    const double n1 = -b - sq, n2 = -b + sq;
+    const bool tiny = (__builtin_fabs(n1) < kTinyNum) | (__builtin_fabs(n2) < kTinyNum);
+    const bool h = need_sq & !tiny & !(n2 < 0.0);
+    r.cold |= need_sq & tiny;
+    r.num = h ? ((n1 < 0.0) ? n2 : n1) : r.num;
+    r.hit |= h;
+  }
+  return r;
+}
+
+// One candidate of a shadow query as the chain of per-lane branches around
+// intersect_num: the form the predicated one below must agree with.
+__host__ __device__ __forceinline__ bool shadow_chain(const SphGeo &s, D3 o, D3 d, double a4, double a2, bool fast,
+                                                      double qlo, double qhi, double dist) {
+  bool occ = false;
+  double num;
+  const int r = fast ? intersect_num(s, o, d, a4, num, qlo) : 2;
+  if (r == 3) {
+    occ = true;
+  } else if (r == 1) {
+    if (num < qlo) occ = true;
+    else if (!(num > qhi)) {
+      const double t = num / a2;
+      occ = t < kInf && t < dist;
+    }
+  } else if (__builtin_expect(r == 2, 0)) {
+    double t;
+    occ = intersect(s, o, d, a4, a2, t) && t < kInf && t < dist;
+  }
+  return occ;
+}
+
+// One candidate of a shadow query (scene.h:78-82: occluded when the sphere
+// reports t < 1e20 and t < dist), qlo / qhi the band of numerators around
+// q = fl(a2 T) that needs the exact division (sweep_shadow).  The band and the
+// cold class are rare: their block is entered by the whole wave when some
+// lane needs it.
+__host__ __device__ __forceinline__ bool shadow_exact(const SphGeo &s, D3 o, D3 d, double a4, double a2, bool fast,
+                                                      double qlo, double qhi, double dist) {
+  const ExactNum r = exact_num<true>(s, o, d, a4, fast, qlo);
+  bool occ = r.early | (r.hit & (r.num < qlo));
+  const bool band = r.hit & !(r.num < qlo) & !(r.num > qhi);
+  if (__builtin_expect(any_lane(band | r.cold), 0)) {
+    if (band) {
+      const double t = r.num / a2;
+      occ = t < kInf && t < dist;
+    }
+    if (r.cold) {
+      double t;
+      occ = intersect(s, o, d, a4, a2, t) && t < kInf && t < dist;
+    }
+  }
+  return occ;
+}
+
 // ---------------------------------------------------------------------------
 // Wave-wide reductions.  Called only where all 64 lanes are active.
 __device__ __forceinline__ double wsum(double v) {
@@ -494,6 +595,9 @@ struct Work {
   // Diagnostic build only (-DRT_STAMPS): s_memtime cycles per phase, per wave.
   unsigned long long st[12] = {};
   unsigned long long iters = 0, sweeps = 0, it_closest = 0, sw_closest = 0, it_prim = 0;
+  // wave-trips through the exact-test loops (RT_TRIP): the shadow lists, the
+  // camera / sphere grid scans, the sweeps' and walks' candidate tests
+  unsigned long long trip_sh = 0, trip_scan = 0, trip_leaf = 0;
 #endif
 };
 #ifdef RT_STAMPS
@@ -509,8 +613,14 @@ __device__ __forceinline__ unsigned long long rt_stamp() {
 #define RT_T0(v) const unsigned long long v = rt_stamp()
 #define RT_ACC(w, slot, v) (w).st[slot] += rt_stamp() - (v)
 #define RT_CNT(w, f, n) (w).f += (n)
+// one count per trip of the wave: its first active lane counts
+#define RT_TRIP(w, f) \
+  do { \
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x & 63)) == (int)(threadIdx.x & 63)) (w).f += 1; \
+  } while (0)
 #else
 #define RT_CNT(w, f, n)
+#define RT_TRIP(w, f)
 #define RT_T0(v)
 #define RT_ACC(w, slot, v)
 #endif
@@ -935,22 +1045,23 @@ __device__ __forceinline__ bool walk4_step(const BvhArgs &bv, const Walk4Ray &r,
 
 // One candidate of the closest-hit search (sweep_closest's exact test): (bt,
 // bi) is the lexicographic (t, index) minimum so far and bn its numerator.
-__device__ __forceinline__ void closest_test(const SphGeo &s, int i, D3 o, D3 d, double a4, double a2, bool fast,
-                                             double &bt, double &bn, int &bi) {
-  double num;
-  const int r = fast ? intersect_num(s, o, d, a4, num) : 2;
-  if (r == 1) {
-    if (num < bn || i < bi) {
-      const double t = num / a2;
-      if (t < bt || (t == bt && i < bi)) {
-        bt = t;
-        bn = num;
-        bi = i;
-      }
-    }
-  } else if (r == 2) {
+// A numerator >= the best's with a larger index cannot win, so it skips the
+// division; the division and the cold class (exact_num) are entered by the
+// whole wave when some lane needs them, and the update is three selects.
+__host__ __device__ __forceinline__ void closest_test(const SphGeo &s, int i, D3 o, D3 d, double a4, double a2,
+                                                      bool fast, double &bt, double &bn, int &bi) {
+  const ExactNum r = exact_num<false>(s, o, d, a4, fast, -1.0);
+  const bool cand = r.hit & ((r.num < bn) | (i < bi));
+  if (any_lane(cand)) {
+    const double t = r.num / a2;
+    const bool win = cand & ((t < bt) | ((t == bt) & (i < bi)));
+    bt = win ? t : bt;
+    bn = win ? r.num : bn;
+    bi = win ? i : bi;
+  }
+  if (__builtin_expect(any_lane(r.cold), 0)) {
     double t;
-    if (intersect(s, o, d, a4, a2, t) && (t < bt || (t == bt && i < bi))) {
+    if (r.cold && intersect(s, o, d, a4, a2, t) && (t < bt || (t == bt && i < bi))) {
       bt = t;
       bn = __builtin_inf();  // no numerator for this best: every later candidate divides
       bi = i;
@@ -1235,25 +1346,8 @@ __device__ __forceinline__ int sweep_closest(const SphGeo *__restrict__ g, const
   // A numerator >= the best's with a larger index cannot win, so it skips the
   // division.
   auto test = [&](int i) {
-    double num;
-    const int r = fast ? intersect_num(g[RT_CK(kCkSphere, i, n)], o, d, a4, num) : 2;
-    if (r == 1) {
-      if (num < bn || i < bi) {
-        const double t = num / a2;
-        if (t < bt || (t == bt && i < bi)) {
-          bt = t;
-          bn = num;
-          bi = i;
-        }
-      }
-    } else if (r == 2) {
-      double t;
-      if (intersect(g[i], o, d, a4, a2, t) && (t < bt || (t == bt && i < bi))) {
-        bt = t;
-        bn = __builtin_inf();  // no numerator for this best: every later candidate divides
-        bi = i;
-      }
-    }
+    RT_TRIP(work, trip_leaf);
+    closest_test(g[RT_CK(kCkSphere, i, n)], i, o, d, a4, a2, fast, bt, bn, bi);
   };
   unsigned long long todo = __ballot(act);
   RT_CNT(work, sw_closest, 1);
@@ -1379,22 +1473,8 @@ __device__ __forceinline__ bool sweep_shadow(const SphGeo *__restrict__ g, const
   const double q = a2 * T, qlo = q * (1.0 - 0x1p-48), qhi = q * (1.0 + 0x1p-48);
   const int lane = (int)(threadIdx.x & 63);
   bool occ = false;
-  auto test = [&](int i) {
-    double num;
-    const int r = fast ? intersect_num(g[RT_CK(kCkSphere, i, n)], o, d, a4, num, qlo) : 2;
-    if (r == 3) {
-      occ = true;
-    } else if (r == 1) {
-      if (num < qlo) occ = true;
-      else if (!(num > qhi)) {
-        const double t = num / a2;
-        occ = t < kInf && t < dist;
-      }
-    } else if (r == 2) {
-      double t;
-      occ = intersect(g[i], o, d, a4, a2, t) && t < kInf && t < dist;
-    }
-  };
+  // called for a lane that is not occluded yet
+  auto test = [&](int i) { occ = shadow_exact(g[RT_CK(kCkSphere, i, n)], o, d, a4, a2, fast, qlo, qhi, dist); };
   const bool have_bvh = kCull && bv.nnodes > 0;
   bool need = false;
   int groups = 0;
@@ -1555,7 +1635,11 @@ __device__ __forceinline__ bool light_common(const LgArgs &lg, LgRange cell, dou
 // same order, so a lane's result is the one the general form gives it.  The
 // exact test's tiny-numerator case (intersect_num's 2) depends on the sphere,
 // not on the light, and stays, as the loop's one cold region.
-template <bool kCommon = false>
+// kPred: a candidate's exact test in its predicated form (shadow_exact);
+// false keeps the chain of per-lane branches (shadow_chain), for the one
+// caller where the predicated form costs registers (the deferred kernels'
+// wide light loop).  The decision is the same.
+template <bool kCommon = false, bool kPred = true>
 __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n, bool act, D3 o, D3 d, D3 lp,
                                              double dist, const LgArgs &lg, int l, LgRange cell, int id0,
                                              Work &work, int pre = -1) {
@@ -1566,21 +1650,10 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
   const bool fast = kCommon || (a2_ok(a2) && dist == dist && T >= 0x1p-900);
   const double q = a2 * T, qlo = q * (1.0 - 0x1p-48), qhi = q * (1.0 + 0x1p-48);
   bool occ = false;
+  // called for a lane that is not occluded yet
   auto test = [&](int i) {
-    double num;
-    const int r = fast ? intersect_num(g[RT_CK(kCkSphere, i, n)], o, d, a4, num, qlo) : 2;
-    if (r == 3) {
-      occ = true;
-    } else if (r == 1) {
-      if (num < qlo) occ = true;
-      else if (!(num > qhi)) {
-        const double t = num / a2;
-        occ = t < kInf && t < dist;
-      }
-    } else if (__builtin_expect(r == 2, 0)) {
-      double t;
-      occ = intersect(g[i], o, d, a4, a2, t) && t < kInf && t < dist;
-    }
+    const SphGeo &s = g[RT_CK(kCkSphere, i, n)];
+    occ = kPred ? shadow_exact(s, o, d, a4, a2, fast, qlo, qhi, dist) : shadow_chain(s, o, d, a4, a2, fast, qlo, qhi, dist);
   };
   // The lane's own sphere `pre` (the shaded point lies on it) is on almost
   // every list, and its test is decided by the first steps of the
@@ -1645,6 +1718,7 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
       if (k < len) nxt = all ? k : lg.ids[RT_CK(kCkLgId, k < len1 ? cell.cb + k : gb + (k - len1), lg.nids)];
       if (i != skip) {
         work.exact += 1;
+        RT_TRIP(work, trip_sh);
         test(i);
       }
     }
@@ -1706,6 +1780,7 @@ __device__ __forceinline__ int grid_closest(const SphGeo *__restrict__ g, int n,
     ++k;
     if (k < len && !all) e = ent[RT_CK(kCkCgEnt, cb + k, nent)];  // the next entry, loaded during this test
     work.exact += 1;
+    RT_TRIP(work, trip_scan);
     closest_test(g[RT_CK(kCkSphere, i, n)], i, o, d, a4, a2, fast, bt, bn, bi);
   }
   best_t = bt;
@@ -1748,6 +1823,7 @@ __device__ __forceinline__ int cam_closest(const SphGeo *__restrict__ g, int n, 
     if (k < len && !all)  // the next entry, loaded during this test
       e = cg.ent[RT_CK(kCkCgEnt, cb + (unsigned)k, (long long)cg.ngrid * cells * kCgSlots)];
     work.exact += 1;
+    RT_TRIP(work, trip_scan);
     closest_test(g[i], i, o, d, a4, a2, fast, bt, bn, bi);
   }
   best_t = bt;

@@ -189,7 +189,10 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, int k) {
 // (rt_device.h light_common, shadow_cells<true>) beside the general one.  The
 // render kernel has it (synth200 0.186 -> 0.181 ms per frame); the deferred
 // kernels and the wide loop do not: there it measured no faster, and in the
-// wide loop it costs 16 more VGPR spills.
+// wide loop it costs 16 more VGPR spills.  The flag
+// also tells the wide loop which kernel it is in: the render kernel's takes
+// the list's exact test in its predicated form (shadow_cells' kPred), the
+// deferred kernels' keeps the chain form.
 template <bool kCull, bool kArgMem = false, bool kFast = false, bool kWide = false, bool kTwoForms = true>
 __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const double *__restrict__ rad,
                                           const SphMat *__restrict__ mat, const LightD *__restrict__ slight, int n,
@@ -253,7 +256,10 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
             const double dist = length(to_light);
             const D3 ldir = normalized(to_light);
             const D3 so = add(hq, scale(ldir, kEps)), sd = renormalized(ldir);
-            const bool occ = shadow_cells(g, n, helper, so, sd, lp, dist, lgw, lh, cell, id0, work, hq_i);
+            // the list's exact test in its predicated form, except in the
+            // deferred kernels (no kTwoForms): there it costs 4 VGPR spills
+            const bool occ =
+                shadow_cells<false, kTwoForms>(g, n, helper, so, sd, lp, dist, lgw, lh, cell, id0, work, hq_i);
             if (helper && !occ) {  // the terms of the loop below, same operands and order
               const double ndl = max0(dot(nq, ldir));
               const D3 diffuse = scale(scale(mc, 1.0 - m.refl), ndl);
@@ -1023,9 +1029,16 @@ __device__ __forceinline__ void merge_tiles(const SphGeo *__restrict__ g, const 
 __device__ __forceinline__ void flush_counts(unsigned long long *counters, const unsigned long long (&sums)[4],
                                              const Work &work) {
   const unsigned long long exact = wave_sum64(work.exact), cull = wave_sum64(work.cull);
+#ifdef RT_STAMPS
+  const unsigned long long trip_sh = wave_sum64(work.trip_sh), trip_scan = wave_sum64(work.trip_scan),
+                           trip_leaf = wave_sum64(work.trip_leaf);
+#endif
   if ((threadIdx.x & 63) == 0) {
     unsigned long long *sc = counter_shard(counters);
 #ifdef RT_STAMPS
+    atomicAdd(&sc[25], trip_sh);
+    atomicAdd(&sc[26], trip_scan);
+    atomicAdd(&sc[27], trip_leaf);
     for (int q = 0; q < 6; q++) atomicAdd(&sc[8 + q], work.st[q]);
     atomicAdd(&sc[20], work.st[6]);
     atomicAdd(&sc[21], work.st[8]);  // closest hits
@@ -3607,6 +3620,11 @@ int rt_render_stats(rt_ctx *c, rt_stats *st) {
       sh += hc[s2 * kShardStride + 22];
     }
     std::fprintf(stderr, "RT_STAMPS cycles/wave: closest hits %.0f, shadow queries %.0f\n", cl / nw, sh / nw);
+    unsigned long long trips[3] = {};
+    for (int s2 = 0; s2 < kShards; s2++)
+      for (int q = 0; q < 3; q++) trips[q] += hc[s2 * kShardStride + 25 + q];
+    std::fprintf(stderr, "RT_STAMPS wave-trips of the exact test: shadow lists %llu, grid scans %llu, sweeps and walks %llu\n",
+                 trips[0], trips[1], trips[2]);
     std::fprintf(stderr, "RT_STAMPS waves=%llu cycles/wave: bound %.0f cull %.0f cand %.0f setup %.0f shade %.0f total %.0f\n",
                  d[6], (double)d[0] / (d[6] ? d[6] : 1), (double)d[1] / (d[6] ? d[6] : 1),
                  (double)d[2] / (d[6] ? d[6] : 1), (double)d[3] / (d[6] ? d[6] : 1),
