@@ -1,9 +1,9 @@
-// The camera grid's device builder (rt_kernel.hip cg_disk_kernel /
-// cg_bin_kernel), per lane: the sphere's disks seen from the grid's point P,
-// and the block / tile / cell tests of the host builder (rt_lightgrid.cpp
-// build_point_grid: the same cube-map patch hierarchy, margins and slack).
-// Host-callable too: tests/native/cg_device_check.cpp runs these same
-// functions, lane by lane, in the kernels' pass structure on the CPU.
+// The device grid builders (rt_gridbuild.h: camera, sphere and light grids),
+// per lane: the sphere's disks seen from the grid's point P, and the block /
+// tile / cell tests of the host builder (rt_lightgrid.cpp build_point_grid:
+// the same cube-map patch hierarchy, margins and slack).  Host-callable too:
+// tests/native/cube_emulate.h runs these same functions, lane by lane, in the
+// kernels' block / quarter / tile / cell order on the CPU.
 #pragma once
 
 #include <cmath>
@@ -79,19 +79,26 @@ RT_HD inline CgDisk cg_side(const CgView &v, int side, int s) {
   return k;
 }
 
+// The cube map's patch tables of one N (cube_tables), wherever they live:
+// N cells, NT tiles, NB blocks per face edge.
+struct CubeTables {
+  const CubePatch *faces, *blocks, *tiles;
+  const double *cell_cbsb;
+  int N, NT, NB;
+};
+
 // Pass 1, lane b: does the disk meet block b's face and block patches?
-RT_HD inline bool cg_block(const CgDisk &k, const CubePatch *faces, const CubePatch *blocks, int NB, int b) {
-  return cg_meets(k, faces[b / (NB * NB)]) && cg_meets(k, blocks[b]);
+RT_HD inline bool cg_block(const CgDisk &k, const CubeTables &T, int b) {
+  return cg_meets(k, T.faces[b / (T.NB * T.NB)]) && cg_meets(k, T.blocks[b]);
 }
 
 // Pass 2, lane = tile (lane & 7, lane >> 3) of block (f, bi, bj): meets the
 // disk (tm); lies well inside it (inside: all its cells listed untested).
-RT_HD inline void cg_tile(const CgDisk &k, const CubePatch *tiles, int NT, int f, int bi, int bj, int lane, bool &tm,
-                          bool &inside) {
+RT_HD inline void cg_tile(const CgDisk &k, const CubeTables &T, int f, int bi, int bj, int lane, bool &tm, bool &inside) {
   const int ti = bi * kCubeB + (lane & 7), tj = bj * kCubeB + (lane >> 3);
   tm = false, inside = false;
-  if (ti < NT && tj < NT) {
-    const CubePatch tp = tiles[((size_t)f * NT + tj) * NT + ti];
+  if (ti < T.NT && tj < T.NT) {
+    const CubePatch tp = T.tiles[((size_t)f * T.NT + tj) * T.NT + ti];
     tm = cg_meets(k, tp);
     inside = tm && k.alpha < 3.0 && k.alpha > tp.rad + 1e-3 &&
              k.ux * tp.cx + k.uy * tp.cy + k.uz * tp.cz >= cos(k.alpha - tp.rad - 1e-3);
@@ -103,8 +110,9 @@ RT_HD inline void cg_tile(const CgDisk &k, const CubePatch *tiles, int NT, int f
 // + i when the disk lists it, else -1 (wide = cg_wide(k)).  The cell's patch: its centre formed
 // as face_dir does, cos / sin of its rad + slack from the per-(i, j) table.
 RT_HD inline bool cg_wide(const CgDisk &k) { return k.alpha + kLgSlack >= 3.0; }
-RT_HD inline int cg_cell(const CgDisk &k, bool wide, const double *cell_cbsb, int N, int f, int bi, int bj, int tl,
-                         int lane, bool tin) {
+RT_HD inline int cg_cell(const CgDisk &k, bool wide, const CubeTables &T, int f, int bi, int bj, int tl, int lane,
+                         bool tin) {
+  const int N = T.N;
   const int i = (bi * kCubeB + (tl & 7)) * kCubeT + (lane & 7), j = (bj * kCubeB + (tl >> 3)) * kCubeT + (lane >> 3);
   bool cm = false;
   if (i < N && j < N) {
@@ -123,7 +131,7 @@ RT_HD inline int cg_cell(const CgDisk &k, bool wide, const double *cell_cbsb, in
       }
       const double l = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
       const size_t ij = (size_t)j * N + i;
-      cm = cg_meets(k, dx / l, dy / l, dz / l, wide ? 3.2 : 0.0, cell_cbsb[2 * ij], cell_cbsb[2 * ij + 1]);
+      cm = cg_meets(k, dx / l, dy / l, dz / l, wide ? 3.2 : 0.0, T.cell_cbsb[2 * ij], T.cell_cbsb[2 * ij + 1]);
     }
   }
   return cm ? (f * N + j) * N + i : -1;

@@ -33,6 +33,7 @@
 
 #include "rt_device.h"
 #include "rt_cgbuild.h"
+#include "rt_gridbuild.h"
 #include "rt_sched.h"
 
 #include <chrono>
@@ -1448,416 +1449,6 @@ __global__ __launch_bounds__(kBlock) void unpermute_kernel(const uint8_t *__rest
   }
 }
 
-// ---------------------------------------------------------------------------
-// The camera grid, built on the device for each camera position of a launch:
-// build_point_grid (rt_lightgrid.cpp) on the GPU.  Every sphere's two disks
-// seen from the grid's point P -- along +u with tlo = (D - R)(1 - 1e-9), along
-// -u (the negative tangent root, sphere.h:43-47) with -(D + R)(1 + 1e-9), R
-// the light grids' grown radius, each disk's angular radius asin(R / D) +
-// kLgSlack -- are listed in every cell they meet, by the host builder's patch
-// hierarchy and tests (faces, blocks of 8 x 8 tiles, tiles of 8 x 8 cells -- a
-// tile well inside a disk takes all its cells untested -- cells against the
-// per-(i, j) table), the same patches and margins; a sphere that contains (or
-// nearly contains) P, or has non-finite data, is one disk of every direction
-// with tlo = -inf (on every list).  A cell keeps K entries; one that
-// overflows is marked by its count, and its rays sweep.  Passes:
-// cg_disk_kernel (a wave per grid and sphere: the disks and the (disk, block)
-// pairs they meet), cg_bin_kernel (a wave per quarter pair: tiles, cells,
-// slots), cg_sort_kernel (a thread per cell: (tlo, index) order).
-struct CgBuild {
-  const SphGeo *geo;
-  const double *rad;
-  const CubePatch *faces, *blocks, *tiles;
-  const double *cell_cbsb;
-  int32_t *count;
-  int2 *ent;            // [grid][cell][K] the lists (count: their lengths)
-  CgDisk *disks;        // [grid][sphere][side]
-  int2 *pairs;          // [grid][maxp] (disk, block) pairs whose block the disk meets
-  unsigned *npairs;     // [grid * kCgCntStride] their counts (a 256-byte line per grid's counter)
-  int n, N, NT, NB, K, ngrid, maxp;
-  double px[RT_MAX_FRAMES], py[RT_MAX_FRAMES], pz[RT_MAX_FRAMES], diam[RT_MAX_FRAMES];
-};
-static_assert(sizeof(CgBuild) <= 4096, "CgBuild exceeds the kernel-argument segment");
-
-constexpr int kCgCntStride = 64;
-// Pass 1, a wave per (grid, sphere): its two disks (one for a global sphere), and
-// every (disk, block) pair whose face and block patches the disk meets (a
-// lane per block, one atomic on the grid's pair count per wave and side).
-__global__ __launch_bounds__(256) void cg_disk_kernel(const CgBuild a) {
-  const int t = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
-  if (t >= a.n * a.ngrid) return;
-  const int grid = t / a.n, s = t - grid * a.n;
-  const SphGeo sp = a.geo[s];
-  const CgView v = cg_view(sp.cx, sp.cy, sp.cz, a.rad[s], a.px[grid], a.py[grid], a.pz[grid], a.diam[grid]);
-  const int nb = 6 * a.NB * a.NB;
-  for (int side = 0; side < (v.global ? 1 : 2); ++side) {
-    const CgDisk k = cg_side(v, side, s);
-    const int di = 2 * t + side;
-    if (lane == 0) a.disks[RT_CK(kCkCgBuild, di, 2LL * a.n * a.ngrid)] = k;
-    for (int b0 = 0; b0 < nb; b0 += 64) {
-      const int b = b0 + lane;
-      const bool m = b < nb && cg_block(k, a.faces, a.blocks, a.NB, b);
-      const unsigned long long bm = __ballot(m);
-      if (!bm) continue;
-      unsigned q0 = 0;
-      if (lane == 0) q0 = atomicAdd(&a.npairs[grid * kCgCntStride], (unsigned)__builtin_popcountll(bm));
-      q0 = (unsigned)__builtin_amdgcn_readfirstlane((int)q0);
-      // a grid whose pairs exceed maxp keeps the first maxp; cg_sort_kernel
-      // then marks all its cells overflowed (its rays sweep)
-      const unsigned qi = q0 + (unsigned)__builtin_popcountll(bm & ((1ull << lane) - 1));
-      if (m && qi < (unsigned)a.maxp) a.pairs[RT_CK(kCkCgBuild, (size_t)grid * a.maxp + qi, (long long)a.ngrid * a.maxp)] =
-          make_int2(di, b);
-    }
-  }
-}
-
-// Pass 2, a wave per quarter of a (disk, block) pair (a fixed grid of waves
-// walks the grids' pair lists): the block's 64 tiles (a tile well inside the
-// disk takes all its cells untested), then the cells of each tile of the
-// quarter it meets; each listed cell takes a slot (count) and, below K, the
-// entry (sphere, tlo).
-__global__ __launch_bounds__(64) void cg_bin_kernel(const CgBuild a) {
-  const int lane = (int)(threadIdx.x & 63);
-  const long long cells = 6LL * a.N * a.N;
-  // work items per grid (4 per stored pair; the host keeps 4 ngrid maxp < 2^32), then their prefix
-  unsigned incl = lane < a.ngrid ? 4u * min(a.npairs[lane * kCgCntStride], (unsigned)a.maxp) : 0u;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned v = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += v;
-  }
-  const unsigned total = __shfl(incl, 63, 64);
-  for (unsigned v = blockIdx.x; v < total; v += gridDim.x) {
-    const int grid = __builtin_popcountll(__ballot(incl <= v));
-    const unsigned item = v - (grid ? __shfl(incl, grid - 1, 64) : 0u);
-    const int2 pr = a.pairs[RT_CK(kCkCgBuild, (size_t)grid * a.maxp + (item >> 2), (long long)a.ngrid * a.maxp)];
-    const CgDisk k = a.disks[RT_CK(kCkCgBuild, pr.x, 2LL * a.n * a.ngrid)];
-    const bool wide = cg_wide(k);
-    const int bb = pr.y;
-    const int f = bb / (a.NB * a.NB), bj = (bb / a.NB) % a.NB, bi = bb % a.NB;
-    bool tm, inside;
-    cg_tile(k, a.tiles, a.NT, f, bi, bj, lane, tm, inside);
-    unsigned long long tmask = __ballot(tm) & (0xffffull << (16 * (item & 3)));
-    const unsigned long long imask = __ballot(inside);
-    while (tmask) {  // up to 4 tiles a round: their cells' slot atomics in flight together
-      int gcs[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        gcs[u] = -1;
-        if (!tmask) continue;
-        const int tl = __builtin_ctzll(tmask);
-        tmask &= tmask - 1;
-        gcs[u] = cg_cell(k, wide, a.cell_cbsb, a.N, f, bi, bj, tl, lane, (imask >> tl) & 1ull);
-      }
-      int slots[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        slots[u] = gcs[u] >= 0 ? atomicAdd(&a.count[RT_CK(kCkCgBuild, (long long)grid * cells + gcs[u], a.ngrid * cells)], 1)
-                               : a.K;
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (slots[u] < a.K)
-          a.ent[RT_CK(kCkCgBuild, ((long long)grid * cells + gcs[u]) * a.K + slots[u], a.ngrid * cells * a.K)] =
-              make_int2(k.s, __float_as_int(k.tlo));
-    }
-  }
-}
-
-// Pass 3, a thread per cell: its list sorted by (tlo, index) in place (lists
-// are short: insertion sort; an overflowed cell's rays sweep, its list unread).
-__global__ __launch_bounds__(256) void cg_sort_kernel(const CgBuild a) {
-  const long long cells = 6LL * a.N * a.N;
-  const long long gc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gc >= cells * a.ngrid) return;
-  if (a.npairs[(gc / cells) * kCgCntStride] > (unsigned)a.maxp) {  // pass 1 dropped pairs: the grid is incomplete
-    a.count[gc] = a.K + 1;                                           // every cell overflowed, its rays sweep
-    return;
-  }
-  const int cnt = a.count[gc];
-  if (cnt > a.K) return;
-  int2 *e = a.ent + gc * a.K;
-  for (int k = 1; k < cnt; ++k) {
-    const int2 x = e[k];
-    const float tx = __int_as_float(x.y);
-    int m = k - 1;
-    while (m >= 0 && (__int_as_float(e[m].y) > tx || (__int_as_float(e[m].y) == tx && e[m].x > x.x))) {
-      e[m + 1] = e[m];
-      --m;
-    }
-    e[m + 1] = x;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Point grids built on the device at upload: the sphere grids
-// (build_sphere_grids, rt_lightgrid.cpp) -- one cube-map grid per reflective
-// sphere s, seen from the ball B(C_s, rho_s) that holds the origins of the
-// reflection rays leaving s (main.cpp:46), both disks of every sphere, the
-// spheres within reach of the ball (global) on every list, entries (sphere,
-// tlo) ascending by (tlo, index) -- and the light grids (build_light_grid)
-// -- one grid per light, seen from the light (rho = 0), the disk ahead only,
-// global spheres on a separate list (the grid's slot `cells`), ids
-// ascending.  The camera grid's per-lane disk / block / tile / cell tests
-// (rt_cgbuild.h) and the host builders' CSR layouts.  Grids go through in
-// batches (their disks and pair lists are scratch); passes:
-//   pg_disk_kernel   a wave per (grid, sphere): its disks and (disk, block)
-//                    pairs (pairs past maxp and global spheres counted per
-//                    grid: the host refuses a sphere grid with more than
-//                    kSgMaxGlobal globals or dropped pairs, as
-//                    build_sphere_grids refuses it); a light grid's global
-//                    sphere goes to its global list (counted, then filled)
-//   pg_bin_kernel    a wave per quarter pair, as cg_bin_kernel: <count> adds
-//                    1 per listed cell, <fill> takes a slot there and writes
-//                    the entry at the cell's CSR offset
-//   scan_*           the exclusive prefix of the counts (CSR offsets)
-//   sg_sort_kernel / ids_sort_kernel   a thread per list: (tlo, index) / (nearest distance, index) order
-//   sg_start_kernel / lg_start_kernel  the host builders' start arrays
-struct GridPt {  // a grid's point and origin-ball radius
-  double x, y, z, rho;
-};
-struct SgBuild {
-  const SphGeo *geo;
-  const double *rad;
-  const GridPt *pts;             // [ng] the batch's grids
-  const unsigned char *allglob;  // [ng] or nullptr: 1 = every sphere global (a non-finite light)
-  const CubePatch *faces, *blocks, *tiles;
-  const double *cell_cbsb;
-  CgDisk *disks;         // [ng][n][2]
-  int2 *pairs;           // [ng][maxp]
-  unsigned *npairs;      // [ng * 16]: pairs per grid (one 64-B line each)
-  unsigned *nglob;       // [ng * 16]: global spheres per grid
-  const unsigned *woff;  // [ng + 1]: work items (4 per kept pair) before grid j; refused grids have none
-  int *cnt;              // [ng][row] (count pass: list lengths; fill pass: slots taken)
-  const int *off;        // [(g0 + j) row + c]: the CSR offset of the batch's grid j's list c
-  int2 *ent;             // sphere grids: (sphere, tlo bits)
-  int32_t *ids;          // light grids: sphere ids
-  long long nent;        // entries of all grids (the fill pass's bound)
-  int n, ng, g0, N, NT, NB, maxp;
-  int row;               // lists per grid: 6 N^2 cells (+ 1 global list: light grids)
-  int sides;             // 2: both disks (sphere grids), 1: the disk ahead (light grids)
-  int globlist;          // 1: global spheres on the grid's list `row - 1`, not in every cell
-  int fill;              // the pass: 0 count, 1 fill
-  double diam;
-};
-static_assert(sizeof(SgBuild) <= 4096, "SgBuild exceeds the kernel-argument segment");
-constexpr int kSgCntStride = 16;
-
-// a list entry: at the CSR offset of list ci (batch-local) plus its slot
-__device__ __forceinline__ void pg_put(const SgBuild &a, long long ci, int slot, int s, float tlo) {
-  const long long e = RT_CK(kCkCgBuild, (long long)a.off[(long long)a.g0 * a.row + ci] + slot, a.nent);
-  if (a.ids)
-    a.ids[e] = s;
-  else
-    a.ent[e] = make_int2(s, __float_as_int(tlo));
-}
-
-__global__ __launch_bounds__(256) void pg_disk_kernel(const SgBuild a) {
-  const int t = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
-  if (t >= a.n * a.ng) return;
-  const int j = t / a.n, i = t - j * a.n;
-  const GridPt P = a.pts[j];
-  const SphGeo sp = a.geo[i];
-  // light grids (one side): spheres within a shadow ray's overshoot of the light are global (kLgOvershoot)
-  CgView v = cg_view(sp.cx, sp.cy, sp.cz, a.rad[i], P.x, P.y, P.z, a.diam, P.rho, a.sides == 1 ? kLgOvershoot : 0.0);
-  if (a.allglob && a.allglob[j]) v = cg_view(0.0, 0.0, 0.0, __builtin_inf(), 0.0, 0.0, 0.0, 0.0);  // global
-  if (v.global && lane == 0) {
-    atomicAdd(&a.nglob[j * kSgCntStride], 1u);
-    if (a.globlist) {  // the grid's global list
-      const long long ci = RT_CK(kCkCgBuild, (long long)j * a.row + a.row - 1, (long long)a.ng * a.row);
-      const int slot = atomicAdd(&a.cnt[ci], 1);
-      if (a.fill) pg_put(a, ci, slot, i, -__builtin_inff());
-    }
-  }
-  if (v.global && a.globlist) return;
-  const int nb = 6 * a.NB * a.NB;
-  for (int side = 0; side < (v.global ? 1 : a.sides); ++side) {
-    const CgDisk k = cg_side(v, side, i);
-    const int di = 2 * t + side;
-    if (lane == 0) a.disks[RT_CK(kCkCgBuild, di, 2LL * a.n * a.ng)] = k;
-    for (int b0 = 0; b0 < nb; b0 += 64) {
-      const int b = b0 + lane;
-      const bool m = b < nb && cg_block(k, a.faces, a.blocks, a.NB, b);
-      const unsigned long long bm = __ballot(m);
-      if (!bm) continue;
-      unsigned q0 = 0;
-      if (lane == 0) q0 = atomicAdd(&a.npairs[j * kSgCntStride], (unsigned)__builtin_popcountll(bm));
-      q0 = (unsigned)__builtin_amdgcn_readfirstlane((int)q0);
-      const unsigned qi = q0 + (unsigned)__builtin_popcountll(bm & ((1ull << lane) - 1));
-      if (m && qi < (unsigned)a.maxp)
-        a.pairs[RT_CK(kCkCgBuild, (size_t)j * a.maxp + qi, (long long)a.ng * a.maxp)] = make_int2(di, b);
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void pg_bin_kernel(const SgBuild a) {
-  const int lane = (int)(threadIdx.x & 63);
-  const unsigned total = a.woff[a.ng];
-  for (unsigned v = blockIdx.x; v < total; v += gridDim.x) {
-    int lo = 0, hi = a.ng;  // the grid of work item v: woff[j] <= v < woff[j + 1]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.woff[mid] <= v) lo = mid; else hi = mid;
-    }
-    const int j = lo;
-    const unsigned item = v - a.woff[j];
-    const int2 pr = a.pairs[RT_CK(kCkCgBuild, (size_t)j * a.maxp + (item >> 2), (long long)a.ng * a.maxp)];
-    const CgDisk k = a.disks[RT_CK(kCkCgBuild, pr.x, 2LL * a.n * a.ng)];
-    const bool wide = cg_wide(k);
-    const int bb = pr.y;
-    const int f = bb / (a.NB * a.NB), bj = (bb / a.NB) % a.NB, bi = bb % a.NB;
-    bool tm, inside;
-    cg_tile(k, a.tiles, a.NT, f, bi, bj, lane, tm, inside);
-    unsigned long long tmask = __ballot(tm) & (0xffffull << (16 * (item & 3)));
-    const unsigned long long imask = __ballot(inside);
-    while (tmask) {
-      const int tl = __builtin_ctzll(tmask);
-      tmask &= tmask - 1;
-      const int gc = cg_cell(k, wide, a.cell_cbsb, a.N, f, bi, bj, tl, lane, (imask >> tl) & 1ull);
-      if (gc >= 0) {
-        const long long ci = RT_CK(kCkCgBuild, (long long)j * a.row + gc, (long long)a.ng * a.row);
-        const int slot = atomicAdd(&a.cnt[ci], 1);
-        if (a.fill) pg_put(a, ci, slot, k.s, k.tlo);
-      }
-    }
-  }
-}
-
-// Exclusive prefix sum of n ints (x -> y, y[n] = the total), in chunks of
-// kScanChunk per 256-thread block: chunk sums, their prefix (one block), then
-// each chunk's prefix from its base.
-constexpr int kScanChunk = 4096;
-__device__ __forceinline__ int block_excl_scan256(int x, int *sh, int &total) {
-  const int t = (int)threadIdx.x;
-  sh[t] = x;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  total = sh[255];
-  const int incl = sh[t];
-  __syncthreads();
-  return incl - x;
-}
-__global__ __launch_bounds__(256) void scan_chunk_sums(const int *x, long long n, long long *bsum) {
-  __shared__ long long sh[256];
-  const long long b0 = (long long)blockIdx.x * kScanChunk;
-  long long s = 0;
-  for (int k = threadIdx.x; k < kScanChunk; k += 256)
-    if (b0 + k < n) s += x[b0 + k];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
-}
-// in place, exclusive, in 64 bits (bsum[nb] = the total: the caller refuses
-// totals past 32 bits before using the offsets); a few thousand chunk sums at
-// most, serially in one thread
-__global__ __launch_bounds__(64) void scan_sums(long long *bsum, int nb) {
-  if (threadIdx.x != 0) return;
-  long long run = 0;
-  for (int k = 0; k < nb; ++k) {
-    const long long v = bsum[k];
-    bsum[k] = run;
-    run += v;
-  }
-  bsum[nb] = run;
-}
-__global__ __launch_bounds__(256) void scan_apply(const int *x, long long n, const long long *bsum, int *y) {
-  __shared__ int sh[256];
-  constexpr int kPer = kScanChunk / 256;
-  const long long b0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kPer;
-  int v[kPer], s = 0;
-#pragma unroll
-  for (int k = 0; k < kPer; ++k) {
-    v[k] = b0 + k < n ? x[b0 + k] : 0;
-    s += v[k];
-  }
-  int tot;
-  int run = (int)bsum[blockIdx.x] + block_excl_scan256(s, sh, tot);
-#pragma unroll
-  for (int k = 0; k < kPer; ++k)
-    if (b0 + k < n) {
-      y[b0 + k] = run;
-      run += v[k];
-    }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) y[n] = (int)bsum[gridDim.x];
-}
-
-// Sphere s's row of CSR starts (every sphere has one, as on the host): its
-// grid's offsets, or an empty list everywhere (no grid / refused).
-__global__ __launch_bounds__(256) void sg_start_kernel(const int *gidx, const unsigned char *ok, const int *off,
-                                                       int n, long long cells, int *start) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x, row = cells + 1;
-  if (k >= (long long)n * row) return;
-  const int s = (int)(k / row);
-  const long long c = k - (long long)s * row;
-  const int j = gidx[s];
-  start[k] = (j >= 0 && ok[j]) ? off[(long long)j * cells + c] : 0;
-}
-
-// A light grid's start row (build_light_grid: stride 6N^2 + 2, the global
-// list last): the CSR offsets of its 6N^2 + 1 lists and their end.
-__global__ __launch_bounds__(256) void lg_start_kernel(const int *off, int nl, long long cells, int *start) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x, row = cells + 2;
-  if (k >= (long long)nl * row) return;
-  const long long l = k / row, c = k - l * row;
-  start[k] = off[l * (cells + 1) + c];  // c = cells + 1: the next light's first offset (or the total)
-}
-
-// A thread per list: ascending ids (insertion sort); with `near` (light
-// grids) ascending by the sphere's nearest distance from the grid's point
-// (|C - P| - |r|, then the id), so a shadow query meets the spheres between
-// its point and the light before those beyond it -- the lists' order is free:
-// a shadow query is an any-hit test (scene.h:78-82).
-__device__ __forceinline__ double near_key(const SphGeo *geo, const GridPt &p, int i) {
-  const SphGeo s = geo[i];
-  const double dx = s.cx - p.x, dy = s.cy - p.y, dz = s.cz - p.z;
-  return __builtin_sqrt(dx * dx + dy * dy + dz * dz) - __builtin_sqrt(s.rr);
-}
-__global__ __launch_bounds__(256) void ids_sort_kernel(const int *off, long long nlists, int32_t *ids,
-                                                       const SphGeo *geo, const GridPt *pts, long long row, int near) {
-  const long long gc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gc >= nlists) return;
-  int32_t *e = ids + off[gc];
-  const int cnt = off[gc + 1] - off[gc];
-  const GridPt p = near ? pts[gc / row] : GridPt{};
-  for (int k = 1; k < cnt; ++k) {
-    const int32_t x = e[k];
-    const double kx = near ? near_key(geo, p, x) : 0.0;
-    int m = k - 1;
-    while (m >= 0) {
-      const double km = near ? near_key(geo, p, e[m]) : 0.0;
-      if (!(kx < km || (!(km < kx) && x < e[m]))) break;
-      e[m + 1] = e[m];
-      --m;
-    }
-    e[m + 1] = x;
-  }
-}
-
-// A thread per cell of every grid: its list in (tlo, index) order (insertion sort).
-__global__ __launch_bounds__(256) void sg_sort_kernel(const int *off, long long ncells, int2 *ent) {
-  const long long gc = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gc >= ncells) return;
-  int2 *e = ent + off[gc];
-  const int cnt = off[gc + 1] - off[gc];
-  for (int k = 1; k < cnt; ++k) {
-    const int2 x = e[k];
-    const float tx = __int_as_float(x.y);
-    int m = k - 1;
-    while (m >= 0 && cg_before(tx, x.x, __int_as_float(e[m].y), e[m].x)) {
-      e[m + 1] = e[m];
-      --m;
-    }
-    e[m + 1] = x;
-  }
-}
-
 }  // namespace rtk
 
 using namespace rtk;
@@ -2099,8 +1690,8 @@ static Knobs read_knobs() {
 // Camera grids (rt_device.h CgArgs), built on the device per camera position
 // of a launch (cg_bin_kernel / cg_sort_kernel) and kept while the positions
 // and the scene stay the same.
-struct CgTables {  // the cube map's patch tables of one N on the device
-  int N = 0, NT = 0, NB = 0;
+struct CgTables {  // the cube map's patch tables of one N on the device: their owners and the kernels' view
+  CubeTables view{};
   DevBuf<CubePatch> faces, blocks, tiles;
   DevBuf<double> cell;
 };
@@ -2312,7 +1903,7 @@ int upload_tables(rt_ctx *c, int N, CgTables &t);
 // kept; replacing one waits for the launches in flight).
 int cg_tables(rt_ctx *c, int N, const CgTables *&out) {
   for (const auto &t : c->cg.tab)
-    if (t.N == N) {
+    if (t.view.N == N) {
       out = &t;
       return RT_OK;
     }
@@ -2336,9 +1927,7 @@ int upload_tables(rt_ctx *c, int N, CgTables &t) {
   RT_TRY(c, t.blocks.upload(blocks));
   RT_TRY(c, t.tiles.upload(tiles));
   RT_TRY(c, t.cell.upload(cell));
-  t.N = N;
-  t.NT = NT;
-  t.NB = NB;
+  t.view = CubeTables{t.faces.get(), t.blocks.get(), t.tiles.get(), t.cell.get(), N, NT, NB};
   return RT_OK;
 }
 
@@ -2424,7 +2013,7 @@ int cam_grid_prepare(rt_ctx *c, const LaunchReq &q, CgPlan &p) {
   const CgTables *tab = nullptr;
   int rc = cg_tables(c, N, tab);
   if (rc != RT_OK) return rc;
-  const long long nblocks = 6LL * tab->NB * tab->NB;
+  const long long nblocks = 6LL * tab->view.NB * tab->view.NB;
   // pairs per grid: every (disk, block) pair at most, within the pair budget
   // (a grid past it is marked overflowed on the device), and 4 work items per
   // pair of all grids countable in 32 bits (cg_bin_kernel)
@@ -2465,14 +2054,11 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
   const size_t cells = 6 * (size_t)p.N * p.N;
   if (p.build) {
     const auto t0 = std::chrono::steady_clock::now();
-    const CgTables *tab = p.tab;
     const int ngrid = p.ngrid;
     CgBuild b{};
-    b.geo = c->scene.geo.get(), b.rad = c->scene.rad.get();
-    b.faces = tab->faces.get(), b.blocks = tab->blocks.get(), b.tiles = tab->tiles.get(), b.cell_cbsb = tab->cell.get();
-    b.count = c->cg.count.get(), b.ent = c->cg.ent.get(), b.disks = c->cg.disks.get();
-    b.pairs = c->cg.pairs.get(), b.npairs = c->cg.npairs.get(), b.maxp = p.maxp;
-    b.n = c->scene.nsph, b.N = p.N, b.NT = tab->NT, b.NB = tab->NB, b.K = kCgSlots, b.ngrid = ngrid;
+    b.j = GridJob{c->scene.geo.get(), c->scene.rad.get(), p.tab->view, c->cg.disks.get(), c->cg.pairs.get(),
+                  c->cg.npairs.get(), c->scene.nsph, ngrid, p.maxp};
+    b.count = c->cg.count.get(), b.ent = c->cg.ent.get(), b.K = kCgSlots;
     for (int g = 0; g < ngrid; g++) {
       b.px[g] = p.pos[3 * g];
       b.py[g] = p.pos[3 * g + 1];
@@ -2480,8 +2066,8 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
       b.diam[g] = extent_with(c->scene, &p.pos[3 * (size_t)g]);  // (the grown radius' margin)
     }
     RT_TRY(c, hipMemsetAsync(b.count, 0, ngrid * cells * sizeof(int32_t), c->stream));
-    RT_TRY(c, hipMemsetAsync(b.npairs, 0, ngrid * kCgCntStride * sizeof(unsigned), c->stream));
-    const int nthr = b.n * ngrid;
+    RT_TRY(c, hipMemsetAsync(b.j.npairs, 0, ngrid * kCgCntStride * sizeof(unsigned), c->stream));
+    const int nthr = b.j.n * ngrid;
     hipLaunchKernelGGL(cg_disk_kernel, dim3((unsigned)((nthr + 3) / 4)), dim3(256), 0, c->stream, b);
     hipLaunchKernelGGL(cg_bin_kernel, dim3((unsigned)std::min<long long>(8192, 8LL * nthr * p.nblocks)), dim3(64), 0,
                        c->stream, b);
@@ -2562,7 +2148,7 @@ int point_grids(rt_ctx *c, int n, const std::vector<GridPt> &pts, const std::vec
   CgTables tab;
   int rc = upload_tables(c, N, tab);
   if (rc != RT_OK) return rc;
-  const long long nblocks = 6LL * tab.NB * tab.NB;
+  const long long nblocks = 6LL * tab.view.NB * tab.view.NB;
   // pairs kept per grid (past it a sphere grid is refused, as one past the
   // host builder's entry cap; a light grid keeps every pair); grids in batches
   // whose disks and pairs fit kPgScratch
@@ -2593,11 +2179,9 @@ int point_grids(rt_ctx *c, int n, const std::vector<GridPt> &pts, const std::vec
   RT_TRY(c, hipMemcpy(d_ag, allglob.data(), (size_t)ng, hipMemcpyHostToDevice));
   RT_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)(ng * row), c->stream));
   SgBuild b{};
-  b.geo = c->scene.geo.get(), b.rad = c->scene.rad.get();
-  b.faces = tab.faces.get(), b.blocks = tab.blocks.get(), b.tiles = tab.tiles.get(), b.cell_cbsb = tab.cell.get();
-  b.disks = d_disks, b.pairs = d_pairs, b.npairs = d_np, b.nglob = d_np + kSgCntStride * (size_t)batch;
-  b.woff = d_woff, b.off = d_off;
-  b.n = n, b.N = N, b.NT = tab.NT, b.NB = tab.NB, b.maxp = (int)maxp, b.row = (int)row;
+  b.j = GridJob{c->scene.geo.get(), c->scene.rad.get(), tab.view, d_disks, d_pairs, d_np, n, 0, (int)maxp};
+  b.nglob = d_np + kSgCntStride * (size_t)batch;
+  b.woff = d_woff, b.off = d_off, b.row = (int)row;
   b.sides = md.sides, b.globlist = md.globlist, b.diam = diam;
   std::vector<std::vector<unsigned>> woffs;
   // one batch of grids: disks and pairs (pass 1) -- and, counting, the
@@ -2606,7 +2190,7 @@ int point_grids(rt_ctx *c, int n, const std::vector<GridPt> &pts, const std::vec
     const int nbg = std::min(batch, ng - g0);
     b.pts = d_pts + g0;
     b.allglob = d_ag + g0;
-    b.ng = nbg;
+    b.j.ng = nbg;
     b.g0 = g0;
     b.cnt = d_cnt + (size_t)g0 * row;
     b.fill = fill ? 1 : 0;
@@ -2657,7 +2241,7 @@ int point_grids(rt_ctx *c, int n, const std::vector<GridPt> &pts, const std::vec
   const long long nlists = (long long)ng * row;
   if (md.globlist)
     hipLaunchKernelGGL(ids_sort_kernel, dim3((unsigned)((nlists + 255) / 256)), dim3(256), 0, c->stream, d_off, nlists,
-                       b.ids, b.geo, d_pts, row, md.near);
+                       b.ids, b.j.geo, d_pts, row, md.near);
   else
     hipLaunchKernelGGL(sg_sort_kernel, dim3((unsigned)((nlists + 255) / 256)), dim3(256), 0, c->stream, d_off, nlists,
                        b.ent);

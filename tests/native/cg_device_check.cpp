@@ -1,10 +1,10 @@
-// Check of the camera grids' device builder (rt_kernel.hip cg_disk_kernel /
-// cg_bin_kernel / cg_sort_kernel) on the CPU: the kernels' per-lane functions
-// (csrc/rt_cgbuild.h, shared with the kernels) run lane by lane in the
-// kernels' pass structure -- pass 1 a wave per (grid, sphere) appending
-// (disk, block) pairs to its grid's list, pass 2 a wave per quarter pair
-// (tiles, then cells of up to 4 tiles a round, slots counted per cell), pass 3
-// the (tlo, index) sort -- for 1-3 camera positions per scene (one grid per
+// Check of the camera grids' device builder (csrc/rt_gridbuild.h
+// cg_disk_kernel / cg_bin_kernel / cg_sort_kernel) on the CPU: the kernels'
+// per-lane functions (csrc/rt_cgbuild.h, shared with the kernels) run lane by
+// lane in the kernels' pass structure -- pass 1 a wave per (grid, sphere)
+// appending (disk, block) pairs to its grid's list, pass 2 a wave per quarter
+// pair (cube_emulate.h: tiles, then cells, slots counted per cell), pass 3 the
+// (tlo, index) sort -- for 1-3 camera positions per scene (one grid per
 // position, as a moving-camera launch builds them).  Checked per grid:
 //   * every cell that did not overflow its K = 48 slots lists exactly the
 //     host builder's entries (build_point_grid, the same N and point), in
@@ -27,6 +27,7 @@
 #include <utility>
 #include <vector>
 
+#include "cube_emulate.h"
 #include "rt_cgbuild.h"
 
 namespace {
@@ -56,7 +57,6 @@ bool hit(V c, double r, V o, V d, double &t) {  // sphere.h:26-59
   if (t < 0) t = std::fmax(t1, t2);
   return true;
 }
-int popc(unsigned long long m) { return __builtin_popcountll(m); }
 
 constexpr int K = 48;  // rt_device.h kCgSlots
 struct Ent {
@@ -72,11 +72,8 @@ struct DevGrids {
 DevGrids build_device(const std::vector<double> &cx, const std::vector<double> &cy, const std::vector<double> &cz,
                       const std::vector<double> &r, const std::vector<V> &pts, const std::vector<double> &diam, int N) {
   const int n = (int)cx.size(), ngrid = (int)pts.size();
-  std::vector<rtk::CubePatch> faces, blocks, tiles;
-  std::vector<double> cell;
-  int NT = 0, NB = 0;
-  rtk::cube_tables(N, faces, blocks, tiles, cell, NT, NB);
-  const int nb = 6 * NB * NB;
+  const cube_emulate::Tables tab(N);
+  const int nb = tab.nblocks();
   const long long cells = 6LL * N * N;
   DevGrids g{N, ngrid, std::vector<int>(ngrid * cells, 0), std::vector<Ent>(ngrid * cells * K)};
   // pass 1
@@ -90,43 +87,20 @@ DevGrids build_device(const std::vector<double> &cx, const std::vector<double> &
       const rtk::CgDisk k = rtk::cg_side(v, side, s);
       const int di = 2 * t + side;
       disks[di] = k;
-      for (int b0 = 0; b0 < nb; b0 += 64)
-        for (int lane = 0; lane < 64; lane++) {
-          const int b = b0 + lane;
-          if (b < nb && rtk::cg_block(k, faces.data(), blocks.data(), NB, b)) pairs[grid].push_back({di, b});
-        }
+      for (int b = 0; b < nb; b++)
+        if (rtk::cg_block(k, tab.view, b)) pairs[grid].push_back({di, b});
     }
   }
-  // pass 2 (quarter items: tiles of rows 2q, 2q + 1 of the block)
+  // pass 2
   for (int grid = 0; grid < ngrid; grid++)
-    for (const auto &pr : pairs[grid])
-      for (int q = 0; q < 4; q++) {
-        const rtk::CgDisk &k = disks[pr.first];
-        const bool wide = rtk::cg_wide(k);
-        const int bb = pr.second;
-        const int f = bb / (NB * NB), bj = (bb / NB) % NB, bi = bb % NB;
-        unsigned long long tmask = 0, imask = 0;
-        for (int lane = 0; lane < 64; lane++) {
-          bool tm, inside;
-          rtk::cg_tile(k, tiles.data(), NT, f, bi, bj, lane, tm, inside);
-          if (tm) tmask |= 1ull << lane;
-          if (inside) imask |= 1ull << lane;
-        }
-        tmask &= 0xffffull << (16 * q);
-        while (tmask) {
-          for (int u = 0; u < 4 && tmask; ++u) {
-            const int tl = __builtin_ctzll(tmask);
-            tmask &= tmask - 1;
-            for (int lane = 0; lane < 64; lane++) {
-              const int gc = rtk::cg_cell(k, wide, cell.data(), N, f, bi, bj, tl, lane, (imask >> tl) & 1ull);
-              if (gc < 0) continue;
-              const long long c = (long long)grid * cells + gc;
-              const int slot = g.count[c]++;
-              if (slot < K) g.ent[c * K + slot] = Ent{k.s, k.tlo};
-            }
-          }
-        }
-      }
+    for (const auto &pr : pairs[grid]) {
+      const rtk::CgDisk &k = disks[pr.first];
+      cube_emulate::block_cells(k, tab.view, pr.second, [&](int gc) {
+        const long long c = (long long)grid * cells + gc;
+        const int slot = g.count[c]++;
+        if (slot < K) g.ent[c * K + slot] = Ent{k.s, k.tlo};
+      });
+    }
   // pass 3
   for (long long c = 0; c < (long long)ngrid * cells; c++) {
     const int cnt = g.count[c];

@@ -1,4 +1,4 @@
-// Check of the device point-grid builder (rt_kernel.hip pg_disk_kernel /
+// Check of the device point-grid builder (csrc/rt_gridbuild.h pg_disk_kernel /
 // pg_bin_kernel / the scan / sg_sort_kernel, ids_sort_kernel / sg_start_kernel,
 // lg_start_kernel) on the CPU, for the sphere grids and the light grids:
 // the kernels' per-lane functions (csrc/rt_cgbuild.h: cg_view with the origin
@@ -6,7 +6,7 @@
 // lane in the kernels' pass structure -- pass 1 a wave per (grid, sphere)
 // appending (disk, block) pairs and counting global spheres, the host's
 // refusal of a grid with more than 32 globals, the bin pass per quarter pair
-// counting then filling CSR lists, the (tlo, index) sort -- against the host
+// (cube_emulate.h) filling CSR lists, the (tlo, index) sort -- against the host
 // builder (rt_lightgrid.cpp build_sphere_grids, the one rt_upload_scene used
 // before) on random scenes: which spheres get a grid, and for every grid and
 // cell the exact list (sphere, tlo bits) in order.  The light grids (one side,
@@ -23,6 +23,7 @@
 #include <random>
 #include <vector>
 
+#include "cube_emulate.h"
 #include "rt_cgbuild.h"
 
 namespace {
@@ -38,11 +39,8 @@ void build_device(const std::vector<double> &cx, const std::vector<double> &cy, 
                   double diam, int N, int max_global, std::vector<unsigned char> &ok,
                   std::vector<std::vector<E>> &lists) {
   const int n = (int)cx.size(), ng = (int)gsph.size();
-  std::vector<rtk::CubePatch> faces, blocks, tiles;
-  std::vector<double> cell;
-  int NT = 0, NB = 0;
-  rtk::cube_tables(N, faces, blocks, tiles, cell, NT, NB);
-  const int nb = 6 * NB * NB;
+  const cube_emulate::Tables tab(N);
+  const int nb = tab.nblocks();
   const long long cells = 6LL * N * N;
   ok.assign((size_t)ng, 0);
   lists.assign((size_t)(ng * cells), {});
@@ -58,34 +56,16 @@ void build_device(const std::vector<double> &cx, const std::vector<double> &cy, 
         const rtk::CgDisk k = rtk::cg_side(v, side, i);
         disks[2 * i + side] = k;
         for (int b = 0; b < nb; b++)
-          if (rtk::cg_block(k, faces.data(), blocks.data(), NB, b)) pairs.push_back({2 * i + side, b});
+          if (rtk::cg_block(k, tab.view, b)) pairs.push_back({2 * i + side, b});
       }
     }
     if (nglob > max_global) continue;  // refused: no lists
     ok[(size_t)j] = 1;
-    for (const auto &pr : pairs)  // the bin pass, all four quarters
-      for (int q = 0; q < 4; q++) {
-        const rtk::CgDisk &k = disks[pr.first];
-        const bool wide = rtk::cg_wide(k);
-        const int bb = pr.second;
-        const int f = bb / (NB * NB), bj = (bb / NB) % NB, bi = bb % NB;
-        unsigned long long tmask = 0, imask = 0;
-        for (int lane = 0; lane < 64; lane++) {
-          bool tm, inside;
-          rtk::cg_tile(k, tiles.data(), NT, f, bi, bj, lane, tm, inside);
-          if (tm) tmask |= 1ull << lane;
-          if (inside) imask |= 1ull << lane;
-        }
-        tmask &= 0xffffull << (16 * q);
-        while (tmask) {
-          const int tl = __builtin_ctzll(tmask);
-          tmask &= tmask - 1;
-          for (int lane = 0; lane < 64; lane++) {
-            const int gc = rtk::cg_cell(k, wide, cell.data(), N, f, bi, bj, tl, lane, (imask >> tl) & 1ull);
-            if (gc >= 0) lists[(size_t)(j * cells + gc)].push_back(E{k.s, k.tlo});
-          }
-        }
-      }
+    for (const auto &pr : pairs) {  // the bin pass
+      const rtk::CgDisk &k = disks[pr.first];
+      cube_emulate::block_cells(k, tab.view, pr.second,
+                                [&](int gc) { lists[(size_t)(j * cells + gc)].push_back(E{k.s, k.tlo}); });
+    }
     for (long long c = 0; c < cells; c++) {  // sg_sort_kernel: insertion sort by (tlo, index)
       std::vector<E> &e = lists[(size_t)(j * cells + c)];
       for (size_t k = 1; k < e.size(); ++k) {
@@ -107,11 +87,8 @@ std::vector<std::vector<int>> build_device_lights(const std::vector<double> &cx,
                                                   const std::vector<double> &lx, const std::vector<double> &ly,
                                                   const std::vector<double> &lz, double diam, int N) {
   const int n = (int)cx.size(), nl = (int)lx.size();
-  std::vector<rtk::CubePatch> faces, blocks, tiles;
-  std::vector<double> cell;
-  int NT = 0, NB = 0;
-  rtk::cube_tables(N, faces, blocks, tiles, cell, NT, NB);
-  const int nb = 6 * NB * NB;
+  const cube_emulate::Tables tab(N);
+  const int nb = tab.nblocks();
   const long long cells = 6LL * N * N, row = cells + 1;
   const double dm = std::isfinite(diam) ? diam : 0.0;
   std::vector<std::vector<int>> lists((size_t)(nl * row));
@@ -125,26 +102,9 @@ std::vector<std::vector<int>> build_device_lights(const std::vector<double> &cx,
         continue;
       }
       const rtk::CgDisk k = rtk::cg_side(v, 0, i);
-      for (int b = 0; b < nb; b++) {
-        if (!rtk::cg_block(k, faces.data(), blocks.data(), NB, b)) continue;
-        const bool wide = rtk::cg_wide(k);
-        const int f = b / (NB * NB), bj = (b / NB) % NB, bi = b % NB;
-        unsigned long long tmask = 0, imask = 0;
-        for (int lane = 0; lane < 64; lane++) {
-          bool tm, inside;
-          rtk::cg_tile(k, tiles.data(), NT, f, bi, bj, lane, tm, inside);
-          if (tm) tmask |= 1ull << lane;
-          if (inside) imask |= 1ull << lane;
-        }
-        while (tmask) {
-          const int tl = __builtin_ctzll(tmask);
-          tmask &= tmask - 1;
-          for (int lane = 0; lane < 64; lane++) {
-            const int gc = rtk::cg_cell(k, wide, cell.data(), N, f, bi, bj, tl, lane, (imask >> tl) & 1ull);
-            if (gc >= 0) lists[(size_t)(l * row + gc)].push_back(i);
-          }
-        }
-      }
+      for (int b = 0; b < nb; b++)
+        if (rtk::cg_block(k, tab.view, b))
+          cube_emulate::block_cells(k, tab.view, b, [&](int gc) { lists[(size_t)(l * row + gc)].push_back(i); });
     }
   }
   // ids_sort_kernel with `near`: each list by (|C - L| - |r|, id), the

@@ -195,7 +195,7 @@ def test_camera_grid_lists_and_scan(tmp_path):
 
 def test_camera_grid_device_builder(tmp_path):
     """The device camera-grid builder's per-lane functions (csrc/rt_cgbuild.h,
-    shared with rt_kernel.hip's cg_disk / cg_bin kernels) run lane by lane in
+    shared with rt_gridbuild.h's cg_disk / cg_bin kernels) run lane by lane in
     the kernels' pass structure on the CPU, 1-3 grids per scene
     (tests/native/cg_device_check.cpp): every cell within its 48 slots lists
     exactly build_point_grid's entries in (tlo, index) order, every sphere the
@@ -215,7 +215,7 @@ def test_camera_grid_device_builder(tmp_path):
 
 
 def test_sphere_grid_device_builder_matches_host(tmp_path):
-    """The device point-grid builder (rt_kernel.hip pg_disk / pg_bin / scan /
+    """The device point-grid builder (rt_gridbuild.h pg_disk / pg_bin / scan /
     sort / start kernels, per-lane functions shared through
     csrc/rt_cgbuild.h) run lane by lane in its pass structure on the CPU
     (tests/native/sg_device_check.cpp) gives, on 120 random scenes (scales
