@@ -1860,6 +1860,17 @@ struct Rows {
   int band, first, stride, count;
 };
 
+// Camera ray direction before normalisation, camera.h:17-25 and main.cpp:150-153:
+// forward + right*((u-0.5)*scale*aspect) + up*((v-0.5)*scale), aspect = 1.0,
+// u = xs/(W-1), v = js/(H-1) (xs, js: the pixel's column and reference row,
+// plus the antialias offsets).  The render kernels and rt_camera_rays share it.
+__device__ __forceinline__ D3 camera_dir(const Cam &cam, double xs, double js, int W, int H) {
+  const double u = xs / (W - 1), v = js / (H - 1);
+  const double su = ((u - 0.5) * cam.scale) * 1.0, sv = (v - 0.5) * cam.scale;
+  return add(add(mk(cam.fx, cam.fy, cam.fz), scale(mk(cam.rx, cam.ry, cam.rz), su)),
+             scale(mk(cam.ux, cam.uy, cam.uz), sv));
+}
+
 __device__ __forceinline__ int quantize(double c) {
   double m = 255.99 * min1(c);  // main.cpp:85
   return (int)m;

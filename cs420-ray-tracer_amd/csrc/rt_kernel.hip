@@ -10,6 +10,8 @@
 // (render_deferred), and each level's (shade*(1-refl), refl) is unwound at the
 // end, which reproduces the reference recursion's rounding exactly.
 // RT_HIP_LDS_SCENE=1 is the first design: 2x2-wave workgroups, scene in LDS.
+// The ray queries (rt_trace_rays, rt_camera_rays: rt_query.h) ask the same
+// sweeps and walks for the closest hit / an occluder of rays the caller supplies.
 //
 // Numerics follow the serial fp64 path operation by operation:
 // vec3.h:13-33, ray.h:12, camera.h:17-25, sphere.h:26-64, scene.h:41-121,
@@ -34,6 +36,7 @@
 #include "rt_device.h"
 #include "rt_cgbuild.h"
 #include "rt_gridbuild.h"
+#include "rt_query.h"
 #include "rt_sched.h"
 
 #include <chrono>
@@ -527,10 +530,7 @@ __device__ __forceinline__ void trace_tile(const SphGeo *__restrict__ g, const d
     // Camera ray, camera.h:17-25 and main.cpp:151-154: ((u-0.5)*scale)*aspect,
     // aspect = 1.0; antialias offsets main_gpu.cu:253-256 (x + 0.0 == x exactly)
     const double ox = (double)(s & 1) * 0.5, oy = s >= 2 ? 0.5 : 0.0;
-    const double u = ((double)x + ox) / (W - 1), v = ((double)j + oy) / (H - 1);
-    const double su = ((u - 0.5) * cam.scale) * 1.0, sv = (v - 0.5) * cam.scale;
-    const D3 dir = add(add(mk(cam.fx, cam.fy, cam.fz), scale(mk(cam.rx, cam.ry, cam.rz), su)),
-                       scale(mk(cam.ux, cam.uy, cam.uz), sv));
+    const D3 dir = camera_dir(cam, (double)x + ox, (double)j + oy, W, H);
     const D3 d = renormalized(normalized(dir));  // get_ray normalises, Ray() normalises again
     const D3 o = mk(cam.px, cam.py, cam.pz);
     const int pix = k * od.xw + (x - od.x0);
@@ -879,10 +879,7 @@ __device__ __forceinline__ void merge_tiles(const SphGeo *__restrict__ g, const 
         const bool in_img = in_tile && y < H;
         const int j = H - 1 - (int)(in_img ? y : 0);  // reference row (main.cpp:74)
         const Cam &cam = kernarg_cam(frame);
-        const double u = (double)x / (W - 1), v = (double)j / (H - 1);
-        const double su = ((u - 0.5) * cam.scale) * 1.0, sv = (v - 0.5) * cam.scale;
-        const D3 dir = add(add(mk(cam.fx, cam.fy, cam.fz), scale(mk(cam.rx, cam.ry, cam.rz), su)),
-                           scale(mk(cam.ux, cam.uy, cam.uz), sv));
+        const D3 dir = camera_dir(cam, (double)x, (double)j, W, H);
         d = renormalized(normalized(dir));
         o = mk(cam.px, cam.py, cam.pz);
         pix = (unsigned)(k * W + x);
@@ -1525,6 +1522,9 @@ struct Scene {
   double c0[3] = {0, 0, 0};
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // bounds of spheres and lights
   double rmax = 0;
+  // the query region R of rt_trace_rays (lo..hi grown on every side by its own
+  // diagonal) and R's diagonal: ray origins inside it keep the walks' margins sound
+  double q_lo[3] = {0, 0, 0}, q_hi[3] = {0, 0, 0}, q_diam = 0;
   std::vector<SchedSphere> refl;  // reflective spheres of the scene (rt_sched.h)
   // BVH over the spheres (fallback for incoherent groups)
   DevBuf<BvhNode> bvh;
@@ -1756,6 +1756,17 @@ struct BuildInfo {
   double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds
 };
 
+// The ray queries' own launch state (rt_trace_rays): nothing of it is shared
+// with the renders.  Created by the first query of a context.
+struct QueryState {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool launched = false;
+  DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
+  PinnedBuf<unsigned long long> host;
+  DevBuf<rt_ray> rays;                 // rt_trace_rays from host memory: the batch on the device
+  DevBuf<rt_hit> hits;
+};
+
 struct rt_ctx {
   explicit rt_ctx(int dev, const Knobs &k) : device(dev), knobs(k) {}
   const int device;
@@ -1774,6 +1785,7 @@ struct rt_ctx {
   LaunchTiming timing;
   OccCache occ;
   BuildInfo info;
+  QueryState query;
   // grow-only scratch of the launches
   DevBuf<uint8_t> tmp;      // rt_render to host memory: the image on the device
   DevBuf<QRay> dq;          // kStackMerge: the deferred queue (and its slots' stacks)
@@ -1830,9 +1842,10 @@ double extent_with(const Scene &sc, const double *p) {
   return std::sqrt(d2);
 }
 
-// BVH arguments for one render: the scene extent includes the camera (the
-// origin of primary rays); margin = 1e-6 * (diameter + largest radius).
-BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
+// BVH arguments for rays whose origins lie within `diam` (a diameter of the
+// scene's bounds extended by them); margin = 1e-6 * (diameter + largest
+// radius).  behind_grid = false: the walks cover the whole line themselves.
+BvhArgs bvh_args_within(const rt_ctx *c, double diam, bool behind_grid) {
   const Scene &sc = c->scene;
   BvhArgs b{};
   b.nodes = sc.bvh.get();
@@ -1853,8 +1866,7 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
   b.ostk = nullptr;  // set in the kernel (LDS), or found at ostk_off
   b.ostk_off = -1;
   b.c0x = sc.c0[0], b.c0y = sc.c0[1], b.c0z = sc.c0[2];
-  const double cp[3] = {cam.px, cam.py, cam.pz};
-  b.diam = extent_with(sc, cp) + 0.01;  // + the 0.001 origin offsets of secondary rays
+  b.diam = diam;
   const double m = 1e-6 * (b.diam + sc.rmax);
   b.margin = std::isfinite(m) ? (float)(m * (1.0 + 1e-6)) : INFINITY;
   b.pmargin = 4.0f * b.margin;
@@ -1867,7 +1879,7 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
   // walks then skip boxes wholly behind the origin
   b.tf_min = -INFINITY;
   b.ug = UgArgs{};
-  if (sc.ug_ok && b.nnodes > 0 && b.ordered && b.wide && std::isfinite(b.pmargin) &&
+  if (behind_grid && sc.ug_ok && b.nnodes > 0 && b.ordered && b.wide && std::isfinite(b.pmargin) &&
       (double)b.pmargin + 1e-4 * (double)sc.ug_extent <= (double)sc.ug_reg_margin) {
     b.ug = sc.ug;
     b.ug.on = 1;
@@ -1880,6 +1892,17 @@ BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
   }
   return b;
 }
+
+// BVH arguments for one render: the scene extent includes the camera (the
+// origin of primary rays).
+BvhArgs bvh_args(const rt_ctx *c, const Cam &cam) {
+  const double cp[3] = {cam.px, cam.py, cam.pz};
+  return bvh_args_within(c, extent_with(c->scene, cp) + 0.01, true);  // + the 0.001 origin offsets of secondary rays
+}
+
+// BVH arguments for a ray query: origins anywhere in the query region
+// (Scene::q_lo..q_hi), no behind grid.
+BvhArgs query_bvh_args(const rt_ctx *c) { return bvh_args_within(c, c->scene.q_diam + 0.01, false); }
 
 LgArgs lg_args(const rt_ctx *c) {
   LgArgs g{};
@@ -3007,6 +3030,8 @@ void rt_destroy(rt_ctx *c) {
     if (c->timing.ev0[i]) (void)hipEventDestroy(c->timing.ev0[i]);
     if (c->timing.ev1[i]) (void)hipEventDestroy(c->timing.ev1[i]);
   }
+  if (c->query.ev0) (void)hipEventDestroy(c->query.ev0);
+  if (c->query.ev1) (void)hipEventDestroy(c->query.ev1);
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;  // the buffers free themselves
@@ -3076,6 +3101,17 @@ static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool wan
     scn.hi[k] = st.hi[k];
   }
   scn.rmax = st.rmax;
+  {  // the query region: the bounds grown on every side by their own diagonal (non-finite bounds: no region)
+    double d2 = 0.0, r2 = 0.0;
+    for (int k = 0; k < 3; k++) d2 += (scn.hi[k] - scn.lo[k]) * (scn.hi[k] - scn.lo[k]);
+    const double diag = std::sqrt(d2);
+    for (int k = 0; k < 3; k++) {
+      scn.q_lo[k] = scn.lo[k] - diag;
+      scn.q_hi[k] = scn.hi[k] + diag;
+      r2 += (scn.q_hi[k] - scn.q_lo[k]) * (scn.q_hi[k] - scn.q_lo[k]);
+    }
+    scn.q_diam = std::sqrt(r2);
+  }
   RT_TRY(c, scn.geo.upload(st.geo, 1));
   RT_TRY(c, scn.rad.upload(st.rad, 1));
   RT_TRY(c, scn.mat.upload(st.mat, 1));
@@ -3262,6 +3298,130 @@ int rt_render_tiles(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, co
   const LaunchReq q{cam, 1, W, H, depth, Rows{1, 0, 1, H}, OutDesc{fb_device, fb_format, 1, 0, W}, tiles, ntiles};
   const int rc = validate(c, q, tiles, ntiles);
   return rc != RT_OK ? rc : enqueue(c, q);
+}
+
+// ---- ray queries (rt_query.h) ----------------------------------------------
+// The checks of the query entry points, before any HIP call.
+static int query_validate(const rt_ctx *c, int mode, const void *rays, size_t n, const void *hits) {
+  if (!c || (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_OCCLUDED) || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (n > 0 && (!rays || !hits)) return RT_ERR_INVALID_ARG;
+  return RT_OK;
+}
+
+// The query path's events, counters and pinned read-back buffer, once per context.
+static int query_state(rt_ctx *c) {
+  QueryState &q = c->query;
+  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
+  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
+  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
+  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
+  if (!q.host.get()) {
+    RT_TRY(c, q.host.alloc(bytes));
+    std::memset(q.host.get(), 0, bytes);
+  }
+  return RT_OK;
+}
+
+int rt_trace_rays_async(rt_ctx *c, int mode, const rt_ray *rays, size_t n, rt_hit *hits) {
+  int rc = query_validate(c, mode, rays, n, hits);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u) return RT_ERR_INVALID_ARG;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  RT_TRY(c, hipSetDevice(c->device));
+  if ((rc = query_state(c)) != RT_OK) return rc;
+  const Scene &sc = c->scene;
+  QueryArgs a{};
+  a.geo = sc.geo.get(), a.rad = sc.rad.get(), a.n = sc.nsph, a.nrays = (int)n;
+  a.accel = c->cull ? 1 : 0;
+  a.rays = rays, a.hits = hits;
+  for (int k = 0; k < 3; k++) a.rlo[k] = sc.q_lo[k], a.rhi[k] = sc.q_hi[k];
+  a.bv = query_bvh_args(c);
+  a.counters = c->query.ctr.get();
+  // the ordered walks' stacks: one wave per workgroup, [entry][lane] at the base of dynamic LDS
+  size_t lds = 0;
+  if (a.bv.ordered) {
+    lds = (size_t)a.bv.odepth * 64 * 8;
+    if (lds <= 12 * 1024) {
+      a.bv.ostk_off = 0;
+    } else {  // deeper than kOrderedStack (bvh_args never allows it): the stackless walk
+      a.bv.ordered = a.bv.wide = 0;
+      lds = 0;
+    }
+  }
+  const long long waves = ((long long)n + 63) / 64;
+  const int grid = (int)std::min<long long>(waves, (long long)c->n_cu * 64);
+  RT_TRY(c, hipMemsetAsync(c->query.ctr.get(), 0, c->query.ctr.bytes(), c->stream));
+  RT_TRY(c, hipEventRecord(c->query.ev0, c->stream));
+  if (mode == RT_QUERY_CLOSEST)
+    hipLaunchKernelGGL(query_kernel<RT_QUERY_CLOSEST>, dim3(grid), dim3(64), lds, c->stream, a);
+  else
+    hipLaunchKernelGGL(query_kernel<RT_QUERY_OCCLUDED>, dim3(grid), dim3(64), lds, c->stream, a);
+  RT_TRY(c, hipGetLastError());
+  RT_TRY(c, hipEventRecord(c->query.ev1, c->stream));
+  c->query.launched = true;
+  return RT_OK;
+}
+
+int rt_trace_stats(rt_ctx *c, rt_query_stats *st) {
+  if (!c || !st) return RT_ERR_INVALID_ARG;
+  *st = rt_query_stats{};
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));
+  if (!c->query.launched) return RT_OK;
+  float ms = 0.f;
+  RT_TRY(c, hipEventElapsedTime(&ms, c->query.ev0, c->query.ev1));
+  unsigned long long *hc = c->query.host.get();
+  RT_TRY(c, hipMemcpy(hc, c->query.ctr.get(), c->query.host.bytes(), hipMemcpyDeviceToHost));
+  unsigned long long sum[kQueryCounters] = {};
+  for (int sh = 0; sh < kShards; sh++)
+    for (int q = 0; q < kQueryCounters; q++) sum[q] += hc[sh * kShardStride + q];
+  st->rays = sum[kQcRays];
+  st->hits = sum[kQcHits];
+  st->tests_exact = sum[kQcExact];
+  st->tests_cull = sum[kQcCull];
+  st->rays_unaccelerated = sum[kQcUnaccel];
+  st->kernel_ms = ms;
+  return RT_OK;
+}
+
+int rt_trace_rays(rt_ctx *c, int mode, const rt_ray *rays, size_t n, rt_hit *hits, int on_device,
+                  rt_query_stats *st) {
+  int rc = query_validate(c, mode, rays, n, hits);
+  if (rc != RT_OK) return rc;
+  if (n == 0) {
+    if (st) *st = rt_query_stats{};
+    return RT_OK;
+  }
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  RT_TRY(c, hipSetDevice(c->device));
+  const rt_ray *d_rays = rays;
+  rt_hit *d_hits = hits;
+  if (!on_device) {
+    if ((rc = grow(c, c->query.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if ((rc = grow(c, c->query.hits, n * sizeof(rt_hit))) != RT_OK) return rc;
+    d_rays = c->query.rays.get(), d_hits = c->query.hits.get();
+    RT_TRY(c, hipMemcpyAsync(c->query.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = rt_trace_rays_async(c, mode, d_rays, n, d_hits)) != RT_OK) return rc;
+  if (!on_device) RT_TRY(c, hipMemcpyAsync(hits, d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
+  rt_query_stats tmp;
+  return rt_trace_stats(c, st ? st : &tmp);
+}
+
+int rt_camera_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows *rows, rt_ray *rays) {
+  if (!c || !cam || !rays || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(rays) & 15u) return RT_ERR_INVALID_ARG;
+  const Rows r = to_rows(rows, H);
+  if (r.band < 1 || r.stride < 1 || r.first < 0 || r.count < 0) return RT_ERR_INVALID_ARG;
+  const long long total = (long long)r.count * W;
+  if (total > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (total == 0) return RT_OK;
+  RT_TRY(c, hipSetDevice(c->device));
+  const unsigned grid = (unsigned)((total + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(grid), dim3(kBlock), 0, c->stream, to_cam(*cam), W, H, r, rays);
+  RT_TRY(c, hipGetLastError());
+  return RT_OK;
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {

@@ -11,6 +11,9 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   trace_ray pixel loop   src/main.cpp:146-157            -> Renderer.render
   launch_gpu_kernel      src/kernel.cu:185-200           -> Renderer.render_async
   write_ppm              src/main.cpp:69-91              -> write_ppm
+  find_intersection      include/scene.h:41-61           -> Renderer.trace_rays (RT_QUERY_CLOSEST)
+  in_shadow (any hit)    include/scene.h:65-86           -> Renderer.trace_rays (RT_QUERY_OCCLUDED)
+  Camera::get_ray        include/camera.h:17-25          -> Renderer.camera_rays
 """
 from __future__ import annotations
 
@@ -98,6 +101,26 @@ class rt_stats(C.Structure):
         return self.rays_primary + self.rays_shadow + self.rays_reflect
 
 
+# Ray queries (rt_trace_rays): a caller's ray, its answer, the launch's counts.
+class rt_ray(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("tmax", C.c_double),
+                ("reserved", C.c_double)]
+
+
+class rt_hit(C.Structure):
+    _fields_ = [("t", C.c_double), ("sphere", C.c_int32), ("occluded", C.c_int32)]
+
+
+class rt_query_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("tests_exact", C.c_uint64), ("tests_cull", C.c_uint64),
+                ("rays_unaccelerated", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+RT_QUERY_CLOSEST, RT_QUERY_OCCLUDED = 0, 1
+
 # Every symbol include/rt_hip.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -130,6 +153,10 @@ SIGNATURES = {
                                   C.c_int, _P]),
     "rt_set_antialias": (C.c_int, [_P, C.c_int]),
     "rt_get_info": (C.c_int, [_P, C.POINTER(rt_info)]),
+    "rt_trace_rays_async": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
+    "rt_trace_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_int, C.POINTER(rt_query_stats)]),
+    "rt_trace_stats": (C.c_int, [_P, C.POINTER(rt_query_stats)]),
+    "rt_camera_rays": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.POINTER(rt_rows), _P]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -399,6 +426,47 @@ class Renderer:
                   rows_per_shard: int):
         _check(self._L.rt_unpermute_rows(self._ctx, C.c_void_p(gathered_ptr), C.c_void_p(image_ptr), width, height,
                                        band, shards, rows_per_shard), "rt_unpermute_rows", self._ctx, L=self._L)
+
+    def trace_rays(self, origins, directions, tmax=None, mode: int = RT_QUERY_CLOSEST):
+        """rt_trace_rays from host memory: ray i = Ray(origins[i], directions[i]) (numpy
+        [n, 3]; any direction length), tmax a scalar or [n] (None = +inf).  Returns
+        (t, sphere, occluded, stats): numpy float64 / int32 / int32 arrays of n and
+        the launch's rt_query_stats."""
+        import numpy as np
+
+        o = np.asarray(origins, np.float64).reshape(-1, 3)
+        d = np.asarray(directions, np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"{n} origins, {d.shape[0]} directions")
+        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax, reserved
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        rays[:, 6] = np.inf if tmax is None else np.broadcast_to(np.asarray(tmax, np.float64), (n,))
+        hits = np.zeros(n, np.dtype([("t", np.float64), ("sphere", np.int32), ("occluded", np.int32)]))
+        st = rt_query_stats()
+        _check(self._L.rt_trace_rays(self._ctx, mode, C.c_void_p(rays.ctypes.data), n, C.c_void_p(hits.ctypes.data), 0,
+                                     C.byref(st)), "rt_trace_rays", self._ctx, L=self._L)
+        return hits["t"].copy(), hits["sphere"].copy(), hits["occluded"].copy(), st
+
+    def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, mode: int = RT_QUERY_CLOSEST):
+        """rt_trace_rays_async: n rt_ray records at rays_ptr, n rt_hit records written at
+        hits_ptr (device memory, 16-byte aligned), enqueued on the context's stream."""
+        _check(self._L.rt_trace_rays_async(self._ctx, mode, C.c_void_p(rays_ptr), n, C.c_void_p(hits_ptr)),
+               "rt_trace_rays_async", self._ctx, L=self._L)
+
+    def trace_stats(self) -> rt_query_stats:
+        """rt_trace_stats: waits for the stream; the most recent query launch."""
+        st = rt_query_stats()
+        _check(self._L.rt_trace_stats(self._ctx, C.byref(st)), "rt_trace_stats", self._ctx, L=self._L)
+        return st
+
+    def camera_rays(self, cam: rt_camera, width: int, height: int, rows: rt_rows | None, rays_ptr: int):
+        """rt_camera_rays: the view's camera rays (get_ray's, camera.h:17-25) as rt_ray
+        records at rays_ptr (device memory, rows.count * width of them), asynchronously."""
+        _check(self._L.rt_camera_rays(self._ctx, C.byref(cam), width, height,
+                                      C.byref(rows) if rows is not None else None, C.c_void_p(rays_ptr)),
+               "rt_camera_rays", self._ctx, L=self._L)
 
     def close(self):
         if self._ctx:

@@ -34,6 +34,12 @@
  *   rt_set_antialias                <- the `-a` flag of ray_gpu, src/main_gpu.cu:249-333, 363-370
  *   rt_get_info                     <- (new) the host-side builds the render calls made (camera grid,
  *                                      tile launch order) and their cost
+ *   rt_trace_rays / rt_trace_rays_async / rt_trace_stats
+ *                                   <- Scene::find_intersection include/scene.h:41-61 (closest hit) and the any-hit
+ *                                      half of Scene::in_shadow include/scene.h:65-86 (occlusion), for rays the
+ *                                      caller supplies; ray i is Ray(origin, direction), include/ray.h:12
+ *   rt_camera_rays                  <- Camera::get_ray        include/camera.h:17-25, per pixel as
+ *                                      src/main.cpp:150-153 calls it: the rays of a view, as rt_ray records
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -41,7 +47,7 @@
  * (the reference's CUDA_CHECK -> exit(1), src/main_gpu.cu:27-35, is not kept).
  * Threading: one rt_ctx per device per host thread; distinct contexts are
  * independent and may be used concurrently.
- * Streams: all device work of a context (renders, rt_unpermute_rows) is
+ * Streams: all device work of a context (renders, ray queries, rt_unpermute_rows) is
  * enqueued on ONE stream, the context's current stream, and is ordered only
  * on it.  The context's own stream (the default) is a BLOCKING stream: it is
  * ordered with the legacy NULL stream, so device buffers a caller fills or
@@ -65,7 +71,8 @@ extern "C" {
                                    11: rt_info BVH / light-grid build times, scratch bytes;
                                    12: rt_info shadow_line_bounded; the rt_group_* entry points were added
                                    under 12 as well (new symbols only: nothing existing changed),
-                                   and so was rt_group_render_frames */
+                                   and so were rt_group_render_frames and the ray queries (rt_trace_rays,
+                                   rt_trace_rays_async, rt_trace_stats, rt_camera_rays) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -311,6 +318,63 @@ int rt_get_info(rt_ctx *ctx, rt_info *out);
  * [H][W][3] image.  Both pointers are device memory; runs on the ctx stream. */
 int rt_unpermute_rows(rt_ctx *ctx, const uint8_t *gathered_device, uint8_t *image_device, int width, int height,
                       int band, int num_shards, int rows_per_shard);
+
+/* ---- ray queries: closest hit and occlusion for the caller's rays ----------
+ * The questions the render loop asks the scene, asked directly: "which sphere
+ * does this ray hit, and where" (Scene::find_intersection, scene.h:41-61) and
+ * "is anything between these two points" (the any-hit half of Scene::in_shadow,
+ * scene.h:65-86), in the reference's fp64 semantics, bit for bit.  There is no
+ * radiance query: per-ray colours could not be pinned to the reference.
+ * Queries are launches of their own: they have their own events and counters,
+ * are not listed by rt_kernel_times, do not change what rt_render_stats or
+ * rt_get_info report, and use none of the render scratch. */
+typedef struct rt_ray {          /* 64 bytes */
+    double origin[3];
+    double direction[3];         /* any length; normalised once by the library, as Ray(o, d) does (ray.h:12, vec3.h:19-20) */
+    double tmax;                 /* occlusion limit along the normalised direction; +inf = none */
+    double reserved;             /* ignored */
+} rt_ray;
+typedef struct rt_hit {          /* 16 bytes */
+    double  t;                   /* closest mode: find_intersection's t; 1e20 on a miss (scene.h:42) */
+    int32_t sphere;              /* closest mode: its sphere index in file order; -1 on a miss */
+    int32_t occluded;            /* 1: some sphere reports a hit with t < 1e20 and t < tmax, else 0 */
+} rt_hit;
+#define RT_QUERY_CLOSEST  0      /* t, sphere and occluded */
+#define RT_QUERY_OCCLUDED 1      /* occluded only (may stop at the first occluder); t = 1e20, sphere = -1 */
+typedef struct rt_query_stats {
+    uint64_t rays, hits;         /* hits: sphere >= 0 (closest) / occluded == 1 (occluded mode) */
+    uint64_t tests_exact, tests_cull;   /* as rt_stats */
+    uint64_t rays_unaccelerated; /* rays answered by the every-sphere sweep: origin outside the query region (or
+                                    not finite), direction not finite once normalised, or culling switched off */
+    double   kernel_ms;          /* HIP-event time of the query kernel */
+} rt_query_stats;
+/* Ray i is the reference's Ray(origin, direction): d = direction.normalized(), once.  Closest mode scans
+   in file order with strict < from 1e20 (ties keep the lowest index); the disc == 0 tangent root is kept
+   even when negative (sphere.h:42-47); a NaN t is never recorded.  `occluded` is in_shadow's test with tmax
+   in place of the light distance (a NaN tmax gives 0; a negative tmax can still be beaten by a negative
+   tangent root).  A zero, NaN or infinite ray is a miss in both modes, never an error.
+   The walks' margins are sized for the query region: the scene's bounding box grown on every side by its
+   own diagonal.  Rays starting outside it test every sphere instead (rays_unaccelerated): the results are
+   exact everywhere, only the speed depends on the region.  rt_set_culling(ctx, 0) makes every ray do so.
+   rays_device / hits_device: device memory of the context's device, 16-byte aligned, n records each.
+   n == 0 is a no-op (RT_OK); n > 2^31-1, a NULL pointer with n > 0 or an unknown mode is
+   RT_ERR_INVALID_ARG (before any HIP call); no uploaded scene is RT_ERR_NO_SCENE.
+   Asynchronous on the context's current stream, ordered as every other launch of the context. */
+int rt_trace_rays_async(rt_ctx *ctx, int mode, const rt_ray *rays_device, size_t n, rt_hit *hits_device);
+/* Synchronous; rays / hits in host memory, or (on_device = 1) device memory as above; stats may be NULL. */
+int rt_trace_rays(rt_ctx *ctx, int mode, const rt_ray *rays, size_t n, rt_hit *hits, int on_device,
+                  rt_query_stats *stats);
+/* Waits for the stream; the counts and time of the most recent query launch (zeros before the first). */
+int rt_trace_stats(rt_ctx *ctx, rt_query_stats *stats);
+/* The camera rays of a view as rt_ray records in DEVICE memory (16-byte aligned, rows->count * width of
+   them; rows = NULL means the full frame): for output row k of `rows` and column x, rays[k*width + x] is the
+   ray get_ray hands to Ray() -- origin = cam->position, direction = the once-normalised
+   forward + right*((u-0.5)*scale) + up*((v-0.5)*scale), u = x/(W-1), v = j/(H-1), j = H-1-y (camera.h:17-25,
+   main.cpp:150-153), tmax = +inf, reserved = 0 -- by the arithmetic of the render kernels' own primary
+   rays.  rt_trace_rays normalises the direction a second time, as Ray() does.  Padding rows (y >= H) get
+   all-zero rays.  Needs no scene.  Asynchronous on the context's stream. */
+int rt_camera_rays(rt_ctx *ctx, const rt_camera *cam, int width, int height, const rt_rows *rows,
+                   rt_ray *rays_device);
 
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
