@@ -11,7 +11,9 @@
 // end, which reproduces the reference recursion's rounding exactly.
 // RT_HIP_LDS_SCENE=1 is the first design: 2x2-wave workgroups, scene in LDS.
 // The ray queries (rt_trace_rays, rt_camera_rays: rt_query.h) ask the same
-// sweeps and walks for the closest hit / an occluder of rays the caller supplies.
+// sweeps and walks for the closest hit / an occluder of rays the caller supplies,
+// the path queries (rt_trace_paths: rt_paths.h) for a ray's whole reflection
+// path with its shadow masks.
 //
 // Numerics follow the serial fp64 path operation by operation:
 // vec3.h:13-33, ray.h:12, camera.h:17-25, sphere.h:26-64, scene.h:41-121,
@@ -37,6 +39,7 @@
 #include "rt_cgbuild.h"
 #include "rt_gridbuild.h"
 #include "rt_query.h"
+#include "rt_paths.h"
 #include "rt_sched.h"
 
 #include <chrono>
@@ -1767,6 +1770,19 @@ struct QueryState {
   DevBuf<rt_hit> hits;
 };
 
+// The path queries' launch state (rt_trace_paths), a sibling of QueryState:
+// shared with neither the renders nor the ray queries.  Created by the first
+// path query of a context.
+struct PathState {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool launched = false;
+  DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
+  PinnedBuf<unsigned long long> host;
+  DevBuf<rt_ray> rays;                 // rt_trace_paths from host memory: the batch on the device
+  DevBuf<rt_vertex> verts;
+  DevBuf<rt_surface> surf;
+};
+
 struct rt_ctx {
   explicit rt_ctx(int dev, const Knobs &k) : device(dev), knobs(k) {}
   const int device;
@@ -1786,6 +1802,7 @@ struct rt_ctx {
   OccCache occ;
   BuildInfo info;
   QueryState query;
+  PathState paths;
   // grow-only scratch of the launches
   DevBuf<uint8_t> tmp;      // rt_render to host memory: the image on the device
   DevBuf<QRay> dq;          // kStackMerge: the deferred queue (and its slots' stacks)
@@ -3032,6 +3049,8 @@ void rt_destroy(rt_ctx *c) {
   }
   if (c->query.ev0) (void)hipEventDestroy(c->query.ev0);
   if (c->query.ev1) (void)hipEventDestroy(c->query.ev1);
+  if (c->paths.ev0) (void)hipEventDestroy(c->paths.ev0);
+  if (c->paths.ev1) (void)hipEventDestroy(c->paths.ev1);
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;  // the buffers free themselves
@@ -3422,6 +3441,131 @@ int rt_camera_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows 
   hipLaunchKernelGGL(camera_rays_kernel, dim3(grid), dim3(kBlock), 0, c->stream, to_cam(*cam), W, H, r, rays);
   RT_TRY(c, hipGetLastError());
   return RT_OK;
+}
+
+// ---- path queries (rt_paths.h) ---------------------------------------------
+// The checks of the path entry points, before any HIP call.
+static int path_validate(const rt_ctx *c, const void *rays, size_t n, int depth, const void *verts) {
+  if (!c || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (n > 0 && (!rays || !verts)) return RT_ERR_INVALID_ARG;
+  if (depth < 1) return RT_ERR_INVALID_ARG;
+  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  if (n == 0) return RT_OK;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  if (c->scene.nlight > RT_PATH_MAX_LIGHTS) return RT_ERR_INVALID_ARG;
+  return RT_OK;
+}
+
+// The path queries' events, counters and pinned read-back buffer, once per context.
+static int path_state(rt_ctx *c) {
+  PathState &q = c->paths;
+  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
+  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
+  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
+  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
+  if (!q.host.get()) {
+    RT_TRY(c, q.host.alloc(bytes));
+    std::memset(q.host.get(), 0, bytes);
+  }
+  return RT_OK;
+}
+
+int rt_trace_paths_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, rt_vertex *verts, rt_surface *surf) {
+  int rc = path_validate(c, rays, n, depth, verts);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(surf)) & 15u)
+    return RT_ERR_INVALID_ARG;
+  RT_TRY(c, hipSetDevice(c->device));
+  if ((rc = path_state(c)) != RT_OK) return rc;
+  const Scene &sc = c->scene;
+  PathArgs a{};
+  a.geo = sc.geo.get(), a.rad = sc.rad.get(), a.mat = sc.mat.get(), a.lights = sc.lights.get();
+  a.n = sc.nsph, a.nl = sc.nlight, a.nrays = (int)n, a.depth = depth;
+  a.accel = c->cull ? 1 : 0;
+  a.rays = rays, a.verts = verts, a.surf = surf;
+  for (int k = 0; k < 3; k++) a.rlo[k] = sc.q_lo[k], a.rhi[k] = sc.q_hi[k];
+  a.bv = query_bvh_args(c);
+  a.counters = c->paths.ctr.get();
+  // the ordered walks' stacks, sized as the query launch sizes them (rt_trace_rays_async)
+  size_t lds = 0;
+  if (a.bv.ordered) {
+    lds = (size_t)a.bv.odepth * 64 * 8;
+    if (lds <= 12 * 1024) {
+      a.bv.ostk_off = 0;
+    } else {
+      a.bv.ordered = a.bv.wide = 0;
+      lds = 0;
+    }
+  }
+  const long long waves = ((long long)n + 63) / 64;
+  const int grid = (int)std::min<long long>(waves, (long long)c->n_cu * 64);
+  RT_TRY(c, hipMemsetAsync(c->paths.ctr.get(), 0, c->paths.ctr.bytes(), c->stream));
+  RT_TRY(c, hipEventRecord(c->paths.ev0, c->stream));
+  if (surf)
+    hipLaunchKernelGGL(path_kernel<true>, dim3(grid), dim3(64), lds, c->stream, a);
+  else
+    hipLaunchKernelGGL(path_kernel<false>, dim3(grid), dim3(64), lds, c->stream, a);
+  RT_TRY(c, hipGetLastError());
+  RT_TRY(c, hipEventRecord(c->paths.ev1, c->stream));
+  c->paths.launched = true;
+  return RT_OK;
+}
+
+int rt_path_stats_get(rt_ctx *c, rt_path_stats *st) {
+  if (!c || !st) return RT_ERR_INVALID_ARG;
+  *st = rt_path_stats{};
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));
+  if (!c->paths.launched) return RT_OK;
+  float ms = 0.f;
+  RT_TRY(c, hipEventElapsedTime(&ms, c->paths.ev0, c->paths.ev1));
+  unsigned long long *hc = c->paths.host.get();
+  RT_TRY(c, hipMemcpy(hc, c->paths.ctr.get(), c->paths.host.bytes(), hipMemcpyDeviceToHost));
+  unsigned long long sum[kPathCounters] = {};
+  for (int sh = 0; sh < kShards; sh++)
+    for (int q = 0; q < kPathCounters; q++) sum[q] += hc[sh * kShardStride + q];
+  st->rays = sum[kPcRays];
+  st->segments = sum[kPcSegments];
+  st->hits = sum[kPcHits];
+  st->shadow_rays = sum[kPcShadow];
+  st->tests_exact = sum[kPcExact];
+  st->tests_cull = sum[kPcCull];
+  st->unaccelerated = sum[kPcUnaccel];
+  st->kernel_ms = ms;
+  return RT_OK;
+}
+
+int rt_trace_paths(rt_ctx *c, const rt_ray *rays, size_t n, int depth, rt_vertex *verts, rt_surface *surf,
+                   int on_device, rt_path_stats *st) {
+  int rc = path_validate(c, rays, n, depth, verts);
+  if (rc != RT_OK) return rc;
+  if (n == 0) {
+    if (st) *st = rt_path_stats{};
+    return RT_OK;
+  }
+  RT_TRY(c, hipSetDevice(c->device));
+  PathState &q = c->paths;
+  const size_t nrec = n * (size_t)depth;
+  const rt_ray *d_rays = rays;
+  rt_vertex *d_verts = verts;
+  rt_surface *d_surf = surf;
+  if (!on_device) {
+    if ((rc = grow(c, q.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if ((rc = grow(c, q.verts, nrec * sizeof(rt_vertex))) != RT_OK) return rc;
+    if (surf && (rc = grow(c, q.surf, nrec * sizeof(rt_surface))) != RT_OK) return rc;
+    d_rays = q.rays.get(), d_verts = q.verts.get(), d_surf = surf ? q.surf.get() : nullptr;
+    RT_TRY(c, hipMemcpyAsync(q.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+    // surfaces of untraced levels are not touched: the caller's bytes travel there and back
+    if (surf) RT_TRY(c, hipMemcpyAsync(d_surf, surf, nrec * sizeof(rt_surface), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = rt_trace_paths_async(c, d_rays, n, depth, d_verts, d_surf)) != RT_OK) return rc;
+  if (!on_device) {
+    RT_TRY(c, hipMemcpyAsync(verts, d_verts, nrec * sizeof(rt_vertex), hipMemcpyDeviceToHost, c->stream));
+    if (surf) RT_TRY(c, hipMemcpyAsync(surf, d_surf, nrec * sizeof(rt_surface), hipMemcpyDeviceToHost, c->stream));
+  }
+  rt_path_stats tmp;
+  return rt_path_stats_get(c, st ? st : &tmp);
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {

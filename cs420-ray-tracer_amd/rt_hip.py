@@ -14,6 +14,7 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   find_intersection      include/scene.h:41-61           -> Renderer.trace_rays (RT_QUERY_CLOSEST)
   in_shadow (any hit)    include/scene.h:65-86           -> Renderer.trace_rays (RT_QUERY_OCCLUDED)
   Camera::get_ray        include/camera.h:17-25          -> Renderer.camera_rays
+  trace_ray's skeleton   src/main.cpp:16-58              -> Renderer.trace_paths (hits, shadow masks, reflections)
 """
 from __future__ import annotations
 
@@ -121,6 +122,49 @@ class rt_query_stats(C.Structure):
 
 RT_QUERY_CLOSEST, RT_QUERY_OCCLUDED = 0, 1
 
+
+# Path queries (rt_trace_paths): a level's vertex, its optional surface record, the launch's counts.
+class rt_vertex(C.Structure):
+    _fields_ = [("t", C.c_double), ("sphere", C.c_int32), ("flags", C.c_int32), ("shadowed", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+class rt_surface(C.Structure):
+    _fields_ = [("dir", C.c_double * 3), ("hit", C.c_double * 3), ("normal", C.c_double * 3),
+                ("view", C.c_double * 3)]
+
+
+class rt_path_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("segments", C.c_uint64), ("hits", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("tests_exact", C.c_uint64), ("tests_cull", C.c_uint64), ("unaccelerated", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+RT_PATH_MAX_LIGHTS = 64
+RT_VERTEX_TRACED, RT_VERTEX_REFLECTS = 1, 2
+# numpy views of rt_vertex / rt_surface records (Renderer.trace_paths); built on first use
+_PATH_DTYPES = {}
+
+
+def _path_dtype(name: str):
+    if not _PATH_DTYPES:
+        import numpy as np
+
+        _PATH_DTYPES["VERTEX_DTYPE"] = np.dtype([("t", np.float64), ("sphere", np.int32), ("flags", np.int32),
+                                                 ("shadowed", np.uint64), ("reserved", np.uint64)])
+        _PATH_DTYPES["SURFACE_DTYPE"] = np.dtype([("dir", np.float64, 3), ("hit", np.float64, 3),
+                                                  ("normal", np.float64, 3), ("view", np.float64, 3)])
+    return _PATH_DTYPES[name]
+
+
+def __getattr__(name):  # VERTEX_DTYPE / SURFACE_DTYPE without importing numpy at module import
+    if name in ("VERTEX_DTYPE", "SURFACE_DTYPE"):
+        return _path_dtype(name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 # Every symbol include/rt_hip.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -157,6 +201,9 @@ SIGNATURES = {
     "rt_trace_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_int, C.POINTER(rt_query_stats)]),
     "rt_trace_stats": (C.c_int, [_P, C.POINTER(rt_query_stats)]),
     "rt_camera_rays": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.POINTER(rt_rows), _P]),
+    "rt_trace_paths_async": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "rt_trace_paths": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, C.c_int, C.POINTER(rt_path_stats)]),
+    "rt_path_stats_get": (C.c_int, [_P, C.POINTER(rt_path_stats)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -467,6 +514,44 @@ class Renderer:
         _check(self._L.rt_camera_rays(self._ctx, C.byref(cam), width, height,
                                       C.byref(rows) if rows is not None else None, C.c_void_p(rays_ptr)),
                "rt_camera_rays", self._ctx, L=self._L)
+
+    def trace_paths(self, origins, directions, depth: int, surfaces: bool = False):
+        """rt_trace_paths from host memory: the path of Ray(origins[i], directions[i]) (numpy
+        [n, 3]; any direction length) through `depth` levels of trace_ray.  Returns
+        (verts, surf, stats): numpy structured arrays shaped [depth, n] of VERTEX_DTYPE and
+        SURFACE_DTYPE (surf is None without `surfaces`; the surface records of untraced
+        levels are zeros) and the launch's rt_path_stats."""
+        import numpy as np
+
+        o = np.asarray(origins, np.float64).reshape(-1, 3)
+        d = np.asarray(directions, np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"{n} origins, {d.shape[0]} directions")
+        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        verts = np.zeros((max(depth, 0), n), _path_dtype("VERTEX_DTYPE"))
+        surf = np.zeros((max(depth, 0), n), _path_dtype("SURFACE_DTYPE")) if surfaces else None
+        st = rt_path_stats()
+        _check(self._L.rt_trace_paths(self._ctx, C.c_void_p(rays.ctypes.data), n, depth, C.c_void_p(verts.ctypes.data),
+                                      C.c_void_p(surf.ctypes.data) if surfaces else None, 0, C.byref(st)),
+               "rt_trace_paths", self._ctx, L=self._L)
+        return verts, surf, st
+
+    def trace_paths_device(self, rays_ptr: int, n: int, depth: int, verts_ptr: int, surf_ptr: int = 0):
+        """rt_trace_paths_async: n rt_ray records at rays_ptr; depth * n rt_vertex records written
+        at verts_ptr and, with surf_ptr, the traced levels' rt_surface records there (device
+        memory, 16-byte aligned, level-major), enqueued on the context's stream."""
+        _check(self._L.rt_trace_paths_async(self._ctx, C.c_void_p(rays_ptr), n, depth, C.c_void_p(verts_ptr),
+                                            C.c_void_p(surf_ptr) if surf_ptr else None),
+               "rt_trace_paths_async", self._ctx, L=self._L)
+
+    def path_stats(self) -> rt_path_stats:
+        """rt_path_stats_get: waits for the stream; the most recent path launch."""
+        st = rt_path_stats()
+        _check(self._L.rt_path_stats_get(self._ctx, C.byref(st)), "rt_path_stats_get", self._ctx, L=self._L)
+        return st
 
     def close(self):
         if self._ctx:

@@ -40,6 +40,11 @@
  *                                      caller supplies; ray i is Ray(origin, direction), include/ray.h:12
  *   rt_camera_rays                  <- Camera::get_ray        include/camera.h:17-25, per pixel as
  *                                      src/main.cpp:150-153 calls it: the rays of a view, as rt_ray records
+ *   rt_trace_paths / rt_trace_paths_async / rt_path_stats_get
+ *                                   <- trace_ray without its colour arithmetic, src/main.cpp:16-58: per level
+ *                                      the closest hit, Scene::in_shadow include/scene.h:65-86 per light as a
+ *                                      bit mask, Sphere::normal_at include/sphere.h:62-64 and the reflection
+ *                                      ray main.cpp:43-48, for rays the caller supplies
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -47,7 +52,7 @@
  * (the reference's CUDA_CHECK -> exit(1), src/main_gpu.cu:27-35, is not kept).
  * Threading: one rt_ctx per device per host thread; distinct contexts are
  * independent and may be used concurrently.
- * Streams: all device work of a context (renders, ray queries, rt_unpermute_rows) is
+ * Streams: all device work of a context (renders, ray and path queries, rt_unpermute_rows) is
  * enqueued on ONE stream, the context's current stream, and is ordered only
  * on it.  The context's own stream (the default) is a BLOCKING stream: it is
  * ordered with the legacy NULL stream, so device buffers a caller fills or
@@ -71,8 +76,9 @@ extern "C" {
                                    11: rt_info BVH / light-grid build times, scratch bytes;
                                    12: rt_info shadow_line_bounded; the rt_group_* entry points were added
                                    under 12 as well (new symbols only: nothing existing changed),
-                                   and so were rt_group_render_frames and the ray queries (rt_trace_rays,
-                                   rt_trace_rays_async, rt_trace_stats, rt_camera_rays) */
+                                   and so were rt_group_render_frames, the ray queries (rt_trace_rays,
+                                   rt_trace_rays_async, rt_trace_stats, rt_camera_rays) and the path queries
+                                   (rt_trace_paths, rt_trace_paths_async, rt_path_stats_get) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -324,7 +330,8 @@ int rt_unpermute_rows(rt_ctx *ctx, const uint8_t *gathered_device, uint8_t *imag
  * does this ray hit, and where" (Scene::find_intersection, scene.h:41-61) and
  * "is anything between these two points" (the any-hit half of Scene::in_shadow,
  * scene.h:65-86), in the reference's fp64 semantics, bit for bit.  There is no
- * radiance query: per-ray colours could not be pinned to the reference.
+ * radiance query: per-ray colours could not be pinned to the reference; the
+ * path queries below return what a caller shades from.
  * Queries are launches of their own: they have their own events and counters,
  * are not listed by rt_kernel_times, do not change what rt_render_stats or
  * rt_get_info report, and use none of the render scratch. */
@@ -375,6 +382,69 @@ int rt_trace_stats(rt_ctx *ctx, rt_query_stats *stats);
    all-zero rays.  Needs no scene.  Asynchronous on the context's stream. */
 int rt_camera_rays(rt_ctx *ctx, const rt_camera *cam, int width, int height, const rt_rows *rows,
                    rt_ray *rays_device);
+
+/* ---- path queries: reflection paths and shadow masks for the caller's rays --
+ * Everything trace_ray (src/main.cpp:16-58) does for a ray except the colour arithmetic: per reflection
+ * level the closest hit, per light whether Scene::in_shadow says shadowed, and the reflection decision --
+ * the geometric skeleton of the ray's path, in the reference's fp64 semantics, bit for bit.  The library
+ * still returns no colour; a caller shades from these records with the reference's Phong
+ * or with a model of its own. */
+#define RT_PATH_MAX_LIGHTS 64            /* bits of rt_vertex.shadowed */
+#define RT_VERTEX_TRACED   1             /* this level's ray was traced */
+#define RT_VERTEX_REFLECTS 2             /* a reflection ray was spawned: the next level is traced */
+typedef struct rt_vertex {               /* 32 bytes */
+    double   t;          /* find_intersection's t of this level's ray; 1e20 on a miss or an untraced level */
+    int32_t  sphere;     /* file-order index; -1 on a miss or an untraced level */
+    int32_t  flags;      /* RT_VERTEX_*; 0 for an untraced level */
+    uint64_t shadowed;   /* bit l: Scene::in_shadow(hit, lights[l]) is true; 0 on a miss / untraced level */
+    uint64_t reserved;   /* written as 0 */
+} rt_vertex;
+typedef struct rt_surface {              /* 96 bytes; optional output */
+    double dir[3];       /* the direction stored in this level's Ray (after Ray()'s normalisation) */
+    double hit[3];       /* ray.origin + ray.direction * t        main.cpp:32 */
+    double normal[3];    /* spheres[sphere].normal_at(hit)        sphere.h:62-64 */
+    double view[3];      /* (ray.origin - hit).normalized()       main.cpp:38 */
+} rt_surface;
+typedef struct rt_path_stats {
+    uint64_t rays;           /* input rays */
+    uint64_t segments;       /* levels traced, over all rays (level 0 included) */
+    uint64_t hits;           /* traced levels that hit a sphere */
+    uint64_t shadow_rays;    /* in_shadow calls: hits x lights */
+    uint64_t tests_exact, tests_cull;   /* as rt_stats */
+    uint64_t unaccelerated;  /* closest-hit and shadow queries answered by the every-sphere sweep */
+    double   kernel_ms;      /* HIP-event time of the path kernel */
+} rt_path_stats;
+/* depth is trace_ray's: 1..RT_MAX_DEPTH levels.  Level 0 is Ray(origin, direction) of rays[i], the direction
+   normalised once as rt_trace_rays does; rt_ray.tmax and reserved are ignored.
+   A traced level k: the closest hit exactly as RT_QUERY_CLOSEST, and on a hit, for every light l in file
+   order, bit l of `shadowed` is the whole of in_shadow (scene.h:65-86): to_light = L - hit, dist its length,
+   ldir = to_light.normalized(), Ray(hit + ldir*EPSILON, ldir) with the direction normalised again by Ray(),
+   shadowed when find_intersection finds a sphere and t < dist.  A light at the hit point gives a NaN
+   direction and is not shadowed.
+   Level k+1 is traced iff level k hit a sphere with reflectivity > 0 and depth - (k+1) >= 1; its ray is
+   Ray(hit + normal*EPSILON, d - normal*2.0*dot(d, normal)) (main.cpp:45-48) and level k carries
+   RT_VERTEX_REFLECTS.  A zero, NaN or infinite ray is a traced miss at level 0, never an error.
+   Layout, level-major: verts[k*n + i] and surf[k*n + i], depth*n records each, 16-byte aligned device
+   memory.  Every rt_vertex of every level is written; untraced levels get {1e20, -1, 0, 0, 0}.  An
+   rt_surface is written only for traced levels (on a traced miss: dir, then zeros); surfaces of untraced
+   levels are not touched.  surf == NULL: no surface is computed or written.
+   Errors, before any HIP call: n == 0 is RT_OK and a no-op; n > 2^31-1, a NULL rays / verts with n > 0 or
+   depth < 1 is RT_ERR_INVALID_ARG; depth > RT_MAX_DEPTH is RT_ERR_DEPTH; no uploaded scene is
+   RT_ERR_NO_SCENE; an uploaded scene of more than RT_PATH_MAX_LIGHTS lights is RT_ERR_INVALID_ARG.
+   Per traced segment and per shadow ray the acceleration rule of rt_trace_rays holds: the culled sweep and
+   the walks when the origin lies in the query region, the normalised direction is finite and culling is on,
+   else the every-sphere sweep (`unaccelerated`); results are exact everywhere.  Shadow queries do not use
+   the light grids (their margins belong to renders), nor does anything here use camera or sphere grids.
+   Path launches have their own events and counters: they are not listed by rt_kernel_times and change
+   nothing that rt_render_stats, rt_get_info or rt_trace_stats report.
+   Asynchronous on the context's current stream, ordered as every other launch of the context. */
+int rt_trace_paths_async(rt_ctx *ctx, const rt_ray *rays_device, size_t n, int depth, rt_vertex *verts_device,
+                         rt_surface *surf_device /* nullable */);
+/* Synchronous; rays / verts / surf in host memory, or (on_device = 1) device memory as above; stats may be NULL. */
+int rt_trace_paths(rt_ctx *ctx, const rt_ray *rays, size_t n, int depth, rt_vertex *verts,
+                   rt_surface *surf /* nullable */, int on_device, rt_path_stats *stats /* nullable */);
+/* Waits for the stream; the counts and time of the most recent path launch (zeros before the first). */
+int rt_path_stats_get(rt_ctx *ctx, rt_path_stats *stats);
 
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
