@@ -138,21 +138,35 @@ __device__ __forceinline__ bool div_num_ok(double x) {
   const double m = __builtin_fabs(x);
   return x == 0.0 || (m >= 0x1p-600 && m <= 0x1p400);
 }
+// The guard and the arithmetic are separate functions, so that a caller can
+// ask the guard of a whole wave and run the arithmetic with no fall-back
+// compiled in; div3's RT_FASTDIV branch is their per-lane composition.
+// div3_shared is plain arithmetic (no trap, no memory): a lane that fails the
+// guard may run it and discard the result.  tests/native/div_check.hip (the
+// composition) and ldir_check.hip (div3_shared formed unguarded, compared
+// where div3_ok holds) prove the same bits as three IEEE divisions on the GPU.
+// No kernel uses either today: as the light direction of shade_hit's common
+// waves, with the guard in light_common, it measured 2.8 % slower
+// (profiles/r14a), as the per-lane form did before.
+__device__ __forceinline__ bool div3_ok(D3 a, double b) {
+  return b >= 0x1p-300 && b <= 0x1p300 && div_num_ok(a.x) && div_num_ok(a.y) && div_num_ok(a.z);
+}
+__device__ __forceinline__ D3 div3_shared(D3 a, double b) {
+  double r = __builtin_amdgcn_rcp(b);
+  double e = __builtin_fma(-b, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  e = __builtin_fma(-b, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  auto one = [&](double x) {
+    const double q = x * r;
+    const double res = __builtin_fma(-b, q, x);
+    return __builtin_copysign(__builtin_fma(res, r, q), x);
+  };
+  return mk(one(a.x), one(a.y), one(a.z));
+}
 __device__ __forceinline__ D3 div3(D3 a, double b) {
 #if RT_FASTDIV
-  if (__builtin_expect(b >= 0x1p-300 && b <= 0x1p300 && div_num_ok(a.x) && div_num_ok(a.y) && div_num_ok(a.z), 1)) {
-    double r = __builtin_amdgcn_rcp(b);
-    double e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    auto one = [&](double x) {
-      const double q = x * r;
-      const double res = __builtin_fma(-b, q, x);
-      return __builtin_copysign(__builtin_fma(res, r, q), x);
-    };
-    return mk(one(a.x), one(a.y), one(a.z));
-  }
+  if (__builtin_expect(div3_ok(a, b), 1)) return div3_shared(a, b);
 #endif
   return mk(a.x / b, a.y / b, a.z / b);
 }
@@ -1592,6 +1606,25 @@ __device__ __forceinline__ int lg_cell_rcp(float ux, float uy, float uz, int N) 
   return (face * N + j) * N + i;
 }
 
+// `st`: the light's row of lg.start (lg.start + l * (6 N^2 + 2)); `room`: the
+// entries of lg.start from `st` on, less one (RT_CHECK bound of a cell index).
+__device__ __forceinline__ LgRange lg_range_row(const int32_t *st, int N, [[maybe_unused]] long long room, D3 hp,
+                                                D3 lp, bool act) {
+  LgRange r{0, 0};
+  if (act) {
+    const int c = lg_cell_rcp((float)(hp.x - lp.x), (float)(hp.y - lp.y), (float)(hp.z - lp.z), N);
+    if (c < 0) {
+      r.cb = -1;
+    } else {
+      const int cc = RT_CK(kCkLgStart, c, room);
+      r.cb = st[cc];
+      r.ce = st[cc + 1];
+    }
+  }
+  return r;
+}
+// The same by the light's index (per lane in the wide light loop): the row
+// address is formed only by the lanes that load through it.
 __device__ __forceinline__ LgRange lg_range(const LgArgs &lg, int l, D3 hp, D3 lp, bool act) {
   LgRange r{0, 0};
   if (act) {
@@ -1613,6 +1646,19 @@ __device__ __forceinline__ int lg_first(const LgArgs &lg, LgRange r) {
   return (r.cb >= 0 && r.ce > r.cb) ? lg.ids[RT_CK(kCkLgId, r.cb, lg.nids)] : 0;
 }
 
+// The light's global list [cb, ce) (the last two entries of its row `st` of
+// lg.start) through the scalar path: the row is the same for every lane, so
+// one scalar load serves the wave and can be issued where the light's
+// iteration starts, well before the list loop needs it.  The cast to the
+// constant address space is what selects the scalar load; it is valid because
+// the grid tables are written by the upload's builder kernels only, never
+// during a render launch.
+__device__ __forceinline__ LgRange lg_global_uniform(const int32_t *st, int cells, [[maybe_unused]] long long room) {
+  typedef const __attribute__((address_space(4))) int32_t CI;
+  CI *p = (CI *)(st + RT_CK(kCkLgStart, cells, room));
+  return LgRange{p[0], p[1]};
+}
+
 // The guards of one light's shadow query that almost every lane passes, as
 // one lane predicate formed from what the light's setup computes anyway: the
 // direction takes renormalized()'s near-one path (`t`: its argument for
@@ -1622,9 +1668,9 @@ __device__ __forceinline__ int lg_first(const LgArgs &lg, LgRange r) {
 // has components RN(x / len) with |len - 1| <= 2u and |x|^2 within 6u of 1, so
 // a = dot(d, d) is within 2^-48 of 1 and a2_ok(2a) holds; dist >= 2^-900 is
 // false for a NaN and is T >= 2^-900 (T = min(dist, kInf)).  A wave whose
-// active lanes all hold it runs shadow_cells<true>.
-__device__ __forceinline__ bool light_common(const LgArgs &lg, LgRange cell, double dist, D3 ldir, double &t) {
-  return renorm_near_one(ldir, t) && lg.off_free && cell.cb >= 0 && dist >= 0x1p-900;
+// active lanes all hold it runs shadow_cells_row<true>.
+__device__ __forceinline__ bool light_common(bool off_free, LgRange cell, double dist, D3 ldir, double &t) {
+  return renorm_near_one(ldir, t) && off_free && cell.cb >= 0 && dist >= 0x1p-900;
 }
 
 // `pre` >= 0: the sphere the shaded point lies on (see below).
@@ -1639,10 +1685,15 @@ __device__ __forceinline__ bool light_common(const LgArgs &lg, LgRange cell, dou
 // false keeps the chain of per-lane branches (shadow_chain), for the one
 // caller where the predicated form costs registers (the deferred kernels'
 // wide light loop).  The decision is the same.
-template <bool kCommon = false, bool kPred = true>
-__device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n, bool act, D3 o, D3 d, D3 lp,
-                                             double dist, const LgArgs &lg, int l, LgRange cell, int id0,
-                                             Work &work, int pre = -1) {
+// global_range(): the light's global list [cb, ce), asked for once the
+// pre-test has left a lane to query -- a per-lane load of the row's last two
+// entries (shadow_cells), or the pair the lane-per-ray loop loaded through the
+// scalar path when the light's iteration began (lg_global_uniform).
+// own (kCommon): g[pre], loaded by the caller where the iteration starts.
+template <bool kCommon = false, bool kPred = true, class GlobalRange>
+__device__ __forceinline__ bool shadow_cells_row(const SphGeo *__restrict__ g, int n, bool act, D3 o, D3 d, D3 lp,
+                                                 double dist, const LgArgs &lg, LgRange cell, int id0, Work &work,
+                                                 int pre, const SphGeo &own, GlobalRange global_range) {
   if (__ballot(act) == 0) return false;
   const double a = dot(d, d);
   const double a4 = 4.0 * a, a2 = 2.0 * a;
@@ -1672,8 +1723,23 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
   //    b (b^2 normal), so n2 = -b + sq < 0 and both roots are negative: a miss; the lists
   //    then skip that sphere.  disc == 0 (the negative tangent root the
   //    reference keeps, sphere.h:43-47) and every other case take the test.
+  // kCommon: the same c, b, p and disc formed by every lane (plain arithmetic
+  // on finite or NaN operands: nothing traps, nothing is stored) and the two
+  // outcomes as lane predicates.  `fast` is true by light_common; a lane the
+  // chain below would lead out by c == 0, b <= 0 or a NaN (every comparison
+  // false) has both predicates false here, as there, and the values it gives
+  // occ and self_miss are the chain's for every other lane: one decision.
   bool self_miss = false;
-  if (act && (kCommon || pre >= 0) && fast) {
+  if constexpr (kCommon) {
+    const SphGeo &s = own;
+    const double ocx = o.x - s.cx, ocy = o.y - s.cy, ocz = o.z - s.cz;
+    const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.rr;
+    const double b = 2.0 * ((ocx * d.x + ocy * d.y) + ocz * d.z);
+    const double p = b * b, disc = p - a4 * c;
+    occ = act & (c < 0.0) & (dist * dist > 6.0 * s.rr) & (s.rr < 1e38) & (s.rr > 1e-200);
+    self_miss = act & (c > 0.0) & (b > 0.0) &
+                ((disc < 0.0) | ((disc > 0.0) & (p > 1e-290) & (disc < p * (1.0 - 0x1p-50))));
+  } else if (act && pre >= 0 && fast) {
     const SphGeo s = g[RT_CK(kCkSphere, pre, n)];
     const double ocx = o.x - s.cx, ocy = o.y - s.cy, ocz = o.z - s.cz;
     const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.rr;
@@ -1687,8 +1753,6 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
   }
   const int skip = self_miss ? pre : -1;
   if (act && !occ) {
-    const int N = lg.N, cells = 6 * N * N;
-    const int32_t *st = lg.start + (size_t)l * (size_t)(cells + 2);
     // The line o + t d passes (up to rounding) through the light; the grid's
     // margins assume it does within max_off -- checked here, per ray, unless
     // the host has bounded it for the whole scene (off_free: |hit point|,
@@ -1706,8 +1770,8 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
     // whose line cannot use the grid tests every sphere (ids 0 .. n-1) in the
     // same loop
     const bool all = !kCommon && (!off_ok || cell.cb < 0);
-    const int cl = RT_CK(kCkLgStart, cells, lg.nstart - 1 - (long long)l * (cells + 2));
-    const int gb = st[cl], ge = st[cl + 1];
+    const LgRange gl = global_range();
+    const int gb = gl.cb, ge = gl.ce;
     const int len1 = all ? n : cell.ce - cell.cb, len = all ? n : len1 + (ge - gb);
     int k = 0;
     int nxt = all ? 0 : id0;
@@ -1724,6 +1788,19 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
     }
   }
   return act && occ;
+}
+// The query of light l by its index (per lane in the wide light loop): the
+// general form, the global list's range loaded by the lanes that need it.
+template <bool kPred = true>
+__device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n, bool act, D3 o, D3 d, D3 lp,
+                                             double dist, const LgArgs &lg, int l, LgRange cell, int id0,
+                                             Work &work, int pre = -1) {
+  return shadow_cells_row<false, kPred>(g, n, act, o, d, lp, dist, lg, cell, id0, work, pre, SphGeo{}, [&] {
+    const int N = lg.N, cells = 6 * N * N;
+    const int32_t *st = lg.start + (size_t)l * (size_t)(cells + 2);
+    const int cl = RT_CK(kCkLgStart, cells, lg.nstart - 1 - (long long)l * (cells + 2));
+    return LgRange{st[cl], st[cl + 1]};
+  });
 }
 
 // Closest hit of camera rays through the camera grid (rt_lightgrid.h

@@ -193,7 +193,7 @@ __device__ __forceinline__ int nth_set_bit(unsigned long long m, int k) {
 // bits, in ceil(lights / lpp) passes instead of one per light.
 // kTwoForms (kFast, the lane-per-ray loop): each light's shadow query has a
 // straight-line form for the waves whose lanes all pass the light's guards
-// (rt_device.h light_common, shadow_cells<true>) beside the general one.  The
+// (rt_device.h light_common, shadow_cells_row<true>) beside the general one.  The
 // render kernel has it (synth200 0.186 -> 0.181 ms per frame); the deferred
 // kernels and the wide loop do not: there it measured no faster, and in the
 // wide loop it costs 16 more VGPR spills.  The flag
@@ -266,7 +266,7 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
             // the list's exact test in its predicated form, except in the
             // deferred kernels (no kTwoForms): there it costs 4 VGPR spills
             const bool occ =
-                shadow_cells<false, kTwoForms>(g, n, helper, so, sd, lp, dist, lgw, lh, cell, id0, work, hq_i);
+                shadow_cells<kTwoForms>(g, n, helper, so, sd, lp, dist, lgw, lh, cell, id0, work, hq_i);
             if (helper && !occ) {  // the terms of the loop below, same operands and order
               const double ndl = max0(dot(nq, ldir));
               const D3 diffuse = scale(scale(mc, 1.0 - m.refl), ndl);
@@ -296,19 +296,58 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
     if (!wide_done && __ballot(hit)) {
       const SphMat m = mat[hi];
       const D3 mc = mk(m.cr, m.cg, m.cb);
+      // kRow (the render kernel's loop, the one with two forms): the light
+      // grid's descriptor is read once per call, and what a light's iteration
+      // needs of it is carried in scalar registers -- the light's row of
+      // lg.start, advanced by the row stride (6 N^2 + 2 entries) per light.
+      // The next light's cell range is loaded from the next row one light
+      // ahead; this light's global-list range is loaded through the scalar path
+      // (lg_global_uniform) and the lane's own sphere, for the query's pre-test,
+      // through the vector path, both where the iteration starts, so they
+      // arrive during the setup arithmetic.  (kFast: the host picked the light
+      // grids, lg.on is set.)  The deferred kernels keep the loop that re-reads
+      // the descriptor where it is used: with the carried row they measured no
+      // faster (profiles/r14a).
+      constexpr bool kRow = kFast && kTwoForms;
+      LgArgs lgv{};  // kRow: the fields the straight-line form reads; the rest stay in the kernarg segment
+      int cells = 0;
+      const int32_t *row = nullptr;
+      [[maybe_unused]] long long room = 0;  // RT_CHECK: entries of lg.start from `row` on, less one
       LgRange next{0, 0};
-      {
+      if constexpr (kRow) {
+        const LgArgs &lgk = kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg);
+        lgv.start = lgk.start, lgv.ids = lgk.ids, lgv.N = lgk.N, lgv.on = lgk.on, lgv.off_free = lgk.off_free;
+#ifdef RT_CHECK
+        lgv.nstart = lgk.nstart, lgv.nids = lgk.nids;
+#endif
+        cells = 6 * lgv.N * lgv.N;
+        row = lgv.start;
+        room = lgv.nstart - 1;
+        if (lgv.on && nl > 0) next = lg_range_row(row, lgv.N, room, hp, mk(slight[0].px, slight[0].py, slight[0].pz), hit);
+      } else {
         const LgArgs &lg0 = kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg);
         if (lg0.on && nl > 0) next = lg_range(lg0, 0, hp, mk(slight[0].px, slight[0].py, slight[0].pz), hit);
       }
       for (int l = 0; l < nl; ++l) {
-        const LgArgs &lg = kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg);
+        const LgArgs &lg = kernarg_late<kArgMem && !kRow, offsetof(RenderArgs, lg)>(lg_arg);
         RT_T0(t_setup);
         // this light's first list id, and the next light's cell range, are
         // loaded now and consumed after the setup arithmetic below
         const LgRange cell = next;
-        const int id0 = lg.on ? lg_first(lg, cell) : 0;
-        if (lg.on && l + 1 < nl) next = lg_range(lg, l + 1, hp, mk(slight[l + 1].px, slight[l + 1].py, slight[l + 1].pz), hit);
+        int id0;
+        [[maybe_unused]] LgRange glob{0, 0};
+        [[maybe_unused]] SphGeo own{};
+        if constexpr (kRow) {
+          id0 = lgv.on ? lg_first(lgv, cell) : 0;
+          if (lgv.on) glob = lg_global_uniform(row, cells, room);
+          if (lgv.on && l + 1 < nl)
+            next = lg_range_row(row + (cells + 2), lgv.N, room - (cells + 2), hp,
+                                mk(slight[l + 1].px, slight[l + 1].py, slight[l + 1].pz), hit);
+          own = g[hi];
+        } else {
+          id0 = lg.on ? lg_first(lg, cell) : 0;
+          if (lg.on && l + 1 < nl) next = lg_range(lg, l + 1, hp, mk(slight[l + 1].px, slight[l + 1].py, slight[l + 1].pz), hit);
+        }
         const LightD L = slight[l];
         const D3 lp = mk(L.px, L.py, L.pz);
         const D3 to_light = sub(lp, hp);
@@ -320,16 +359,20 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
         bool occ = false;
         if (__ballot(need)) {
           const D3 so = add(hp, scale(ldir, kEps));
-          if constexpr (kFast && kTwoForms) {
+          if constexpr (kRow) {
             // a wave with no rare lane for this light (light_common) takes the
-            // query's straight-line form; any other wave the general one
+            // query's straight-line form; any other wave the general one, with
+            // the descriptor read from the kernarg segment there, where it is rare
+            auto global_range = [&] { return glob; };
             double rt;
-            const bool common = light_common(lg, cell, dist, ldir, rt);
+            const bool common = light_common(lgv.off_free, cell, dist, ldir, rt);
             if (__ballot(need && !common) == 0)
-              occ = shadow_cells<true>(g, n, need, so, renorm_near_one_quot(ldir, rt), lp, dist, lg, l, cell, id0,
-                                       work, hi);
+              occ = shadow_cells_row<true>(g, n, need, so, renorm_near_one_quot(ldir, rt), lp, dist, lgv, cell, id0, work,
+                                           hi, own, global_range);
             else
-              occ = shadow_cells(g, n, need, so, renormalized(ldir), lp, dist, lg, l, cell, id0, work, hi);
+              occ = shadow_cells_row(g, n, need, so, renormalized(ldir), lp, dist,
+                                     kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg), cell, id0, work, hi, own,
+                                     global_range);
           } else if constexpr (kFast) {
             occ = shadow_cells(g, n, need, so, renormalized(ldir), lp, dist, lg, l, cell, id0, work, hi);
           } else {
@@ -356,6 +399,10 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
           col = add(add(specular, diffuse), col);                  // scene.h:117
         }
         RT_ACC(work, 4, t_shade);
+        if constexpr (kRow) {
+          row += cells + 2;
+          room -= cells + 2;
+        }
       }
     }
   if (hit) {
