@@ -174,6 +174,19 @@ __device__ __forceinline__ D3 normalized(D3 a) {
   double len = length(a);
   return div3(a, len);  // vec3.h:26-29: x/len, y/len, z/len
 }
+// The binary exponent e of x = f 2^e, 0.5 <= |f| < 1 (v_frexp_exp_i32_f64); 0
+// for a zero, an infinity and a NaN.  The host form serves the CPU checks.
+__host__ __device__ __forceinline__ int frexp_exp(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_frexp_exp(x);
+#else
+  int e = 0;
+  if (x == 0.0 || !(__builtin_fabs(x) < __builtin_inf())) return 0;
+  (void)__builtin_frexp(x, &e);
+  return e;
+#endif
+}
+
 // normalized(a), bit-identical, with a fast path for |a| within a few ulps of
 // 1 -- the renderer normalises already-normalised directions again (Ray()'s
 // constructor, ray.h:12: the camera ray and the shadow direction, scene.h:72)
@@ -195,11 +208,26 @@ __device__ __forceinline__ D3 normalized(D3 a) {
 // The two halves are separate so that a caller can ask a whole wave for the
 // fast path first (renorm_near_one) and then run it with no fall-back compiled
 // in (renorm_near_one_quot): renormalized() is the per-lane composition.
-__device__ __forceinline__ bool renorm_near_one(D3 a, double &t) {
+// The guard is two compares (tests/native/predicate_forms_check.cpp):
+//  * -4 <= t <= 6 as |t - 1| <= half_width = 5.  t - 1 is exact for t in
+//    [-7, -4] and [4, 8) (t is a multiple of 2^-50 there and so is t - 1,
+//    which stays below 8 in magnitude: 53 bits), so the neighbours of -4 and
+//    6 give values just outside [-5, 5]; rounding is monotonic, so every t
+//    beyond them does, and every t inside stays inside; a NaN fails both forms.  A caller with a wave-uniform reason
+//    to refuse the fast path passes a negative width (light_common).
+//  * |x| >= 2^-959 or x == 0 for the three components as one compare on the
+//    smallest binary exponent: frexp_exp is >= -958 exactly for |x| >= 2^-959
+//    and is 0 for a zero; it is 0 too for an infinity or a NaN, which the
+//    range test has refused already (s is then infinite or NaN).
+__host__ __device__ __forceinline__ bool renorm_t_ok(double t, double half_width) {
+  return __builtin_fabs(t - 1.0) <= half_width;
+}
+__host__ __device__ __forceinline__ bool renorm_near_one(D3 a, double &t, double half_width = 5.0) {
   const double s = (a.x * a.x + a.y * a.y) + a.z * a.z;
   t = (s - 1.0) * 0x1p53;
-  auto usable = [](double x) { return __builtin_fabs(x) >= 0x1p-959 || x == 0.0; };
-  return t >= -4.0 && t <= 6.0 && usable(a.x) && usable(a.y) && usable(a.z);
+  const int ex = frexp_exp(a.x), ey = frexp_exp(a.y), ez = frexp_exp(a.z);
+  const int e = ex < ey ? (ex < ez ? ex : ez) : (ey < ez ? ey : ez);
+  return renorm_t_ok(t, half_width) && e >= -958;
 }
 __device__ __forceinline__ D3 renorm_near_one_quot(D3 a, double t) {
   constexpr double u = 0x1p-53;
@@ -1668,9 +1696,13 @@ __device__ __forceinline__ LgRange lg_global_uniform(const int32_t *st, int cell
 // has components RN(x / len) with |len - 1| <= 2u and |x|^2 within 6u of 1, so
 // a = dot(d, d) is within 2^-48 of 1 and a2_ok(2a) holds; dist >= 2^-900 is
 // false for a NaN and is T >= 2^-900 (T = min(dist, kInf)).  A wave whose
-// active lanes all hold it runs shadow_cells_row<true>.
-__device__ __forceinline__ bool light_common(bool off_free, LgRange cell, double dist, D3 ldir, double &t) {
-  return renorm_near_one(ldir, t) && off_free && cell.cb >= 0 && dist >= 0x1p-900;
+// active lanes all hold it runs shadow_cells_row<true>.  off_free is the
+// scene's, the same for every lane and light of a call: the caller folds it
+// into the width of the near-one range test once (light_common_width: no t
+// has |t - 1| <= -1), instead of a term of every lane's predicate.
+__host__ __device__ __forceinline__ double light_common_width(bool off_free) { return off_free ? 5.0 : -1.0; }
+__host__ __device__ __forceinline__ bool light_common(double width, LgRange cell, double dist, D3 ldir, double &t) {
+  return renorm_near_one(ldir, t, width) && cell.cb >= 0 && dist >= 0x1p-900;
 }
 
 // `pre` >= 0: the sphere the shaded point lies on (see below).
@@ -1815,6 +1847,20 @@ __device__ __forceinline__ bool shadow_cells(const SphGeo *__restrict__ g, int n
 // over all spheres, as sweep_closest's.  A lane whose direction cannot be
 // binned tests every sphere; a lane whose cell overflowed the builder's K
 // slots is told to sweep.
+// The scan loops below (cam_closest, grid_closest) have two forms, as the
+// shadow query has (shadow_cells_row's kCommon): a wave whose scanning lanes
+// all have a2_ok(a2) and a binnable cell runs the loop with `fast` and `all`
+// compiled out -- the same operations on the same operands in the same order
+// for each of its lanes -- and any other wave (a NaN or unnormalised
+// direction in some lane) runs the loop as written.  A lane that does not scan
+// (inactive, or told to sweep: len = 0) joins either.
+template <bool kCommon>
+struct ScanForm {
+  static constexpr bool value = kCommon;
+};
+__device__ __forceinline__ bool scan_common(bool act, bool fast, bool all) {
+  return __ballot(act && (all || !fast)) == 0;
+}
 constexpr int kCgSlots = 48;  // entries per cell; a cell with more has its rays sweep
 struct CgArgs {
   const int32_t *count;   // [grid][6N^2] entries of each cell (> kCgSlots: overflowed, its rays sweep)
@@ -1849,17 +1895,23 @@ __device__ __forceinline__ int grid_closest(const SphGeo *__restrict__ g, int n,
       len = start[sbase + cc + 1] - cb;
     }
   }
-  int k = 0;
-  int2 e = (len > 0 && !all) ? ent[RT_CK(kCkCgEnt, cb, nent)] : make_int2(0, (int)0xff800000u);  // -inf
-  while (k < len) {
-    const int i = all ? k : e.x;
-    if ((double)__int_as_float(e.y) > bt) break;
-    ++k;
-    if (k < len && !all) e = ent[RT_CK(kCkCgEnt, cb + k, nent)];  // the next entry, loaded during this test
-    work.exact += 1;
-    RT_TRIP(work, trip_scan);
-    closest_test(g[RT_CK(kCkSphere, i, n)], i, o, d, a4, a2, fast, bt, bn, bi);
-  }
+  auto scan = [&](auto common) {
+    constexpr bool kCommon = decltype(common)::value;
+    const bool fs = kCommon || fast, al = !kCommon && all;
+    int k = 0;
+    int2 e = (len > 0 && !al) ? ent[RT_CK(kCkCgEnt, cb, nent)] : make_int2(0, (int)0xff800000u);  // -inf
+    while (k < len) {
+      const int i = al ? k : e.x;
+      if ((double)__int_as_float(e.y) > bt) break;
+      ++k;
+      if (k < len && !al) e = ent[RT_CK(kCkCgEnt, cb + k, nent)];  // the next entry, loaded during this test
+      work.exact += 1;
+      RT_TRIP(work, trip_scan);
+      closest_test(g[RT_CK(kCkSphere, i, n)], i, o, d, a4, a2, fs, bt, bn, bi);
+    }
+  };
+  if (scan_common(act, fast, all)) scan(ScanForm<true>{});
+  else scan(ScanForm<false>{});
   best_t = bt;
   return bi;
 }
@@ -1890,19 +1942,25 @@ __device__ __forceinline__ int cam_closest(const SphGeo *__restrict__ g, int n, 
       cb = gc * (unsigned)kCgSlots;
     }
   }
-  int k = 0;
-  int2 e = (len > 0 && !all) ? cg.ent[RT_CK(kCkCgEnt, cb, (long long)cg.ngrid * cells * kCgSlots)]
-                              : make_int2(0, (int)0xff800000u);  // -inf
-  while (k < len) {
-    const int i = all ? k : RT_CK(kCkSphere, e.x, n);
-    if ((double)__int_as_float(e.y) > bt) break;
-    ++k;
-    if (k < len && !all)  // the next entry, loaded during this test
-      e = cg.ent[RT_CK(kCkCgEnt, cb + (unsigned)k, (long long)cg.ngrid * cells * kCgSlots)];
-    work.exact += 1;
-    RT_TRIP(work, trip_scan);
-    closest_test(g[i], i, o, d, a4, a2, fast, bt, bn, bi);
-  }
+  auto scan = [&](auto common) {
+    constexpr bool kCommon = decltype(common)::value;
+    const bool fs = kCommon || fast, al = !kCommon && all;
+    int k = 0;
+    int2 e = (len > 0 && !al) ? cg.ent[RT_CK(kCkCgEnt, cb, (long long)cg.ngrid * cells * kCgSlots)]
+                               : make_int2(0, (int)0xff800000u);  // -inf
+    while (k < len) {
+      const int i = al ? k : RT_CK(kCkSphere, e.x, n);
+      if ((double)__int_as_float(e.y) > bt) break;
+      ++k;
+      if (k < len && !al)  // the next entry, loaded during this test
+        e = cg.ent[RT_CK(kCkCgEnt, cb + (unsigned)k, (long long)cg.ngrid * cells * kCgSlots)];
+      work.exact += 1;
+      RT_TRIP(work, trip_scan);
+      closest_test(g[i], i, o, d, a4, a2, fs, bt, bn, bi);
+    }
+  };
+  if (scan_common(act, fast, all)) scan(ScanForm<true>{});
+  else scan(ScanForm<false>{});
   best_t = bt;
   return bi;
 }

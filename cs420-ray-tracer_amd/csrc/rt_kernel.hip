@@ -304,16 +304,21 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
       // ahead; this light's global-list range is loaded through the scalar path
       // (lg_global_uniform) and the lane's own sphere, for the query's pre-test,
       // through the vector path, both where the iteration starts, so they
-      // arrive during the setup arithmetic.  (kFast: the host picked the light
-      // grids, lg.on is set.)  The deferred kernels keep the loop that re-reads
-      // the descriptor where it is used: with the carried row they measured no
-      // faster (profiles/r14a).
+      // arrive during the setup arithmetic.  The deferred kernels keep the loop
+      // that re-reads the descriptor where it is used: with the carried row they
+      // measured no faster (profiles/r14a).
+      // kRow has no test of lg.on: launch_tiles sets `sel.fast = merge &&
+      // bv.ordered && bv.wide && ra.lg.on`, and render_kernel_fn picks a kFast
+      // kernel only from sel.fast (sel.wide implies it), so the test is
+      // constant in this loop.  What is wave-uniform per call is decided
+      // once here: off_free, as the width of light_common's range test.
       constexpr bool kRow = kFast && kTwoForms;
       LgArgs lgv{};  // kRow: the fields the straight-line form reads; the rest stay in the kernarg segment
       int cells = 0;
       const int32_t *row = nullptr;
       [[maybe_unused]] long long room = 0;  // RT_CHECK: entries of lg.start from `row` on, less one
       LgRange next{0, 0};
+      [[maybe_unused]] double common_width = 0.0;
       if constexpr (kRow) {
         const LgArgs &lgk = kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg);
         lgv.start = lgk.start, lgv.ids = lgk.ids, lgv.N = lgk.N, lgv.on = lgk.on, lgv.off_free = lgk.off_free;
@@ -323,7 +328,8 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
         cells = 6 * lgv.N * lgv.N;
         row = lgv.start;
         room = lgv.nstart - 1;
-        if (lgv.on && nl > 0) next = lg_range_row(row, lgv.N, room, hp, mk(slight[0].px, slight[0].py, slight[0].pz), hit);
+        common_width = light_common_width(lgv.off_free != 0);
+        if (nl > 0) next = lg_range_row(row, lgv.N, room, hp, mk(slight[0].px, slight[0].py, slight[0].pz), hit);
       } else {
         const LgArgs &lg0 = kernarg_late<kArgMem, offsetof(RenderArgs, lg)>(lg_arg);
         if (lg0.on && nl > 0) next = lg_range(lg0, 0, hp, mk(slight[0].px, slight[0].py, slight[0].pz), hit);
@@ -338,9 +344,9 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
         [[maybe_unused]] LgRange glob{0, 0};
         [[maybe_unused]] SphGeo own{};
         if constexpr (kRow) {
-          id0 = lgv.on ? lg_first(lgv, cell) : 0;
-          if (lgv.on) glob = lg_global_uniform(row, cells, room);
-          if (lgv.on && l + 1 < nl)
+          id0 = lg_first(lgv, cell);
+          glob = lg_global_uniform(row, cells, room);
+          if (l + 1 < nl)
             next = lg_range_row(row + (cells + 2), lgv.N, room - (cells + 2), hp,
                                 mk(slight[l + 1].px, slight[l + 1].py, slight[l + 1].pz), hit);
           own = g[hi];
@@ -365,7 +371,7 @@ __device__ __forceinline__ void shade_hit(const SphGeo *__restrict__ g, const do
             // the descriptor read from the kernarg segment there, where it is rare
             auto global_range = [&] { return glob; };
             double rt;
-            const bool common = light_common(lgv.off_free, cell, dist, ldir, rt);
+            const bool common = light_common(common_width, cell, dist, ldir, rt);
             if (__ballot(need && !common) == 0)
               occ = shadow_cells_row<true>(g, n, need, so, renorm_near_one_quot(ldir, rt), lp, dist, lgv, cell, id0, work,
                                            hi, own, global_range);
