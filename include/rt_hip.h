@@ -163,7 +163,11 @@ typedef struct rt_stats {
     uint64_t rays_primary;
     uint64_t rays_shadow;
     uint64_t rays_reflect;
-    uint64_t negative_clamped; /* channels whose int(255.99*min(1,c)) < 0, stored as 0 */
+    uint64_t negative_clamped; /* channels whose int(255.99*min(1,c)) < 0, stored as 0: RT_FB_RGB8 output only
+                                  (RT_FB_F32X3 / RT_FB_F64X3 are unquantised and count 0).  A NaN channel is
+                                  outside the contract ((int)NaN is undefined in the reference): the device
+                                  stores 0 for it without counting it, an x86 host converts it to INT_MIN
+                                  and counts it. */
     double kernel_ms;
     uint64_t tests_exact;      /* exact ray-sphere tests executed (sphere.h:26-59), live lanes only */
     uint64_t tests_cull;       /* sphere-vs-wave-bound tests (one per sphere per wave sweep) */
@@ -253,7 +257,10 @@ int rt_kernel_times(rt_ctx *ctx, double *ms_out, int max_n, int *n_out);
 #define RT_FB_RGB8 0  /* uint8 RGB, width*height*3, PPM row order (top row first), quantised as write_ppm */
 #define RT_FB_F32X3 1 /* float RGB per pixel at index y*width + x, y = 0 the BOTTOM row: the reference's
                          d_framebuffer of launch_gpu_kernel (kernel.cu:112), unquantised */
-#define RT_FB_F64X3 2 /* double RGB (Vec3) per pixel, same indexing: the serial framebuffer, main.cpp:156 */
+#define RT_FB_F64X3 2 /* double RGB (Vec3) per pixel, same indexing: the serial framebuffer, main.cpp:156.
+                         Numerically the reference's; a zero channel may differ in sign: a hit of
+                         reflectivity > 1 with no depth left stores col*(1-refl) = -0.0 where the
+                         reference adds (0,0,0)*refl and has +0.0 */
 
 /* launch_gpu_kernel (src/kernel.cu:185-200) with its tile semantics: renders
  * pixels x in [tile_x, tile_x + tile_w), y in [tile_y, tile_y + tile_h)
