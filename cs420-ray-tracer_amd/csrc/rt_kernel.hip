@@ -13,7 +13,8 @@
 // The ray queries (rt_trace_rays, rt_camera_rays: rt_query.h) ask the same
 // sweeps and walks for the closest hit / an occluder of rays the caller supplies,
 // the path queries (rt_trace_paths: rt_paths.h) for a ray's whole reflection
-// path with its shadow masks.
+// path with its shadow masks, and the radiance queries (rt_trace_radiance:
+// rt_radiance.h) shade and composite that path into trace_ray's colour.
 //
 // Numerics follow the serial fp64 path operation by operation:
 // vec3.h:13-33, ray.h:12, camera.h:17-25, sphere.h:26-64, scene.h:41-121,
@@ -40,6 +41,7 @@
 #include "rt_gridbuild.h"
 #include "rt_query.h"
 #include "rt_paths.h"
+#include "rt_radiance.h"
 #include "rt_sched.h"
 
 #include <chrono>
@@ -1836,6 +1838,19 @@ struct PathState {
   DevBuf<rt_surface> surf;
 };
 
+// The radiance queries' launch state (rt_trace_radiance), a sibling of
+// PathState: shared with neither the renders nor the other queries.  Created
+// by the first radiance query of a context.
+struct RadianceState {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool launched = false;
+  DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
+  PinnedBuf<unsigned long long> host;
+  DevBuf<StackEnt> stack;              // grow-only: [depth - 1][grid * 64] of the largest launch seen
+  DevBuf<rt_ray> rays;                 // rt_trace_radiance from host memory: the batch on the device
+  DevBuf<uint8_t> out;
+};
+
 struct rt_ctx {
   explicit rt_ctx(int dev, const Knobs &k) : device(dev), knobs(k) {}
   const int device;
@@ -1856,6 +1871,7 @@ struct rt_ctx {
   BuildInfo info;
   QueryState query;
   PathState paths;
+  RadianceState radiance;
   // grow-only scratch of the launches
   DevBuf<uint8_t> tmp;      // rt_render to host memory: the image on the device
   DevBuf<QRay> dq;          // kStackMerge: the deferred queue (and its slots' stacks)
@@ -3104,6 +3120,8 @@ void rt_destroy(rt_ctx *c) {
   if (c->query.ev1) (void)hipEventDestroy(c->query.ev1);
   if (c->paths.ev0) (void)hipEventDestroy(c->paths.ev0);
   if (c->paths.ev1) (void)hipEventDestroy(c->paths.ev1);
+  if (c->radiance.ev0) (void)hipEventDestroy(c->radiance.ev0);
+  if (c->radiance.ev1) (void)hipEventDestroy(c->radiance.ev1);
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;  // the buffers free themselves
@@ -3619,6 +3637,149 @@ int rt_trace_paths(rt_ctx *c, const rt_ray *rays, size_t n, int depth, rt_vertex
   }
   rt_path_stats tmp;
   return rt_path_stats_get(c, st ? st : &tmp);
+}
+
+// ---- radiance queries (rt_radiance.h) --------------------------------------
+// Bytes of one output record; 0 for an unknown format.
+static size_t radiance_record(int fmt) {
+  return fmt == RT_FB_RGB8 ? 3 : fmt == RT_FB_F32X3 ? 3 * sizeof(float) : fmt == RT_FB_F64X3 ? 3 * sizeof(double) : 0;
+}
+
+// The checks of the radiance entry points, before any HIP call.
+static int radiance_validate(const rt_ctx *c, const void *rays, size_t n, int depth, int fmt, const void *out) {
+  if (!c || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (n > 0 && (!rays || !out)) return RT_ERR_INVALID_ARG;
+  if (depth < 1 || radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
+  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  if (n == 0) return RT_OK;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  return RT_OK;
+}
+
+// The radiance queries' events, counters and pinned read-back buffer, once per context.
+static int radiance_state(rt_ctx *c) {
+  RadianceState &q = c->radiance;
+  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
+  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
+  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
+  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
+  if (!q.host.get()) {
+    RT_TRY(c, q.host.alloc(bytes));
+    std::memset(q.host.get(), 0, bytes);
+  }
+  return RT_OK;
+}
+
+// The most reflection-stack scratch a radiance launch takes.  A launch of
+// `grid` one-wave workgroups at `depth` needs grid * 64 * (depth - 1) entries
+// of 32 bytes: 32 MiB per level below the first for the full grid of 64 waves
+// per CU on 256 CUs.  Depths up to 9 fit; a deeper launch gets a smaller grid
+// (at depth 64 still 2080 waves, two per SIMD of such a device), never a
+// larger budget ("Radiance").
+constexpr size_t kRadianceStackBudget = 256u << 20;
+
+int rt_trace_radiance_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out) {
+  int rc = radiance_validate(c, rays, n, depth, fmt, out);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+  RT_TRY(c, hipSetDevice(c->device));
+  if ((rc = radiance_state(c)) != RT_OK) return rc;
+  const Scene &sc = c->scene;
+  RadianceState &rs = c->radiance;
+  RadianceArgs a{};
+  PathArgs &p = a.q;
+  p.geo = sc.geo.get(), p.rad = sc.rad.get(), p.mat = sc.mat.get(), p.lights = sc.lights.get();
+  p.n = sc.nsph, p.nl = sc.nlight, p.nrays = (int)n, p.depth = depth;
+  p.accel = c->cull ? 1 : 0;
+  p.rays = rays;
+  for (int k = 0; k < 3; k++) p.rlo[k] = sc.q_lo[k], p.rhi[k] = sc.q_hi[k];
+  p.bv = query_bvh_args(c);
+  p.counters = rs.ctr.get();
+  a.amb = D3{sc.amb[0], sc.amb[1], sc.amb[2]};
+  a.fmt = fmt, a.out = out;
+  // the ordered walks' stacks, sized as the path launch sizes them (rt_trace_paths_async)
+  size_t lds = 0;
+  if (p.bv.ordered) {
+    lds = (size_t)p.bv.odepth * 64 * 8;
+    if (lds <= 12 * 1024) {
+      p.bv.ostk_off = 0;
+    } else {
+      p.bv.ordered = p.bv.wide = 0;
+      lds = 0;
+    }
+  }
+  a.park_off = (int)lds;  // the wave's parked colours behind them
+  lds += 64 * sizeof(D3);
+  const long long waves = ((long long)n + 63) / 64;
+  long long grid = std::min<long long>(waves, (long long)c->n_cu * 64);
+  // the reflection stack belongs to the launch's lane slots, so the grid bounds it, not n; depth 1
+  // spawns nothing and takes none
+  if (depth > 1) {
+    const size_t per_wave = (size_t)64 * (size_t)(depth - 1) * sizeof(StackEnt);
+    grid = std::min<long long>(grid, std::max<long long>(1, (long long)(kRadianceStackBudget / per_wave)));
+    if ((rc = grow(c, rs.stack, (size_t)grid * per_wave)) != RT_OK) return rc;
+    a.stack = rs.stack.get();
+  }
+  a.sstride = (unsigned)grid * 64u;
+  RT_TRY(c, hipMemsetAsync(rs.ctr.get(), 0, rs.ctr.bytes(), c->stream));
+  RT_TRY(c, hipEventRecord(rs.ev0, c->stream));
+  hipLaunchKernelGGL(radiance_kernel, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
+  RT_TRY(c, hipGetLastError());
+  RT_TRY(c, hipEventRecord(rs.ev1, c->stream));
+  rs.launched = true;
+  return RT_OK;
+}
+
+int rt_radiance_stats_get(rt_ctx *c, rt_radiance_stats *st) {
+  if (!c || !st) return RT_ERR_INVALID_ARG;
+  *st = rt_radiance_stats{};
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));
+  RadianceState &rs = c->radiance;
+  if (!rs.launched) return RT_OK;
+  float ms = 0.f;
+  RT_TRY(c, hipEventElapsedTime(&ms, rs.ev0, rs.ev1));
+  unsigned long long *hc = rs.host.get();
+  RT_TRY(c, hipMemcpy(hc, rs.ctr.get(), rs.host.bytes(), hipMemcpyDeviceToHost));
+  unsigned long long sum[kRadianceCounters] = {};
+  for (int sh = 0; sh < kShards; sh++)
+    for (int q = 0; q < kRadianceCounters; q++) sum[q] += hc[sh * kShardStride + q];
+  st->rays = sum[kPcRays];
+  st->segments = sum[kPcSegments];
+  st->hits = sum[kPcHits];
+  st->shadow_rays = sum[kPcShadow];
+  st->tests_exact = sum[kPcExact];
+  st->tests_cull = sum[kPcCull];
+  st->unaccelerated = sum[kPcUnaccel];
+  st->negative_clamped = sum[kRcNegative];
+  st->kernel_ms = ms;
+  return RT_OK;
+}
+
+int rt_trace_radiance(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out, int on_device,
+                      rt_radiance_stats *st) {
+  int rc = radiance_validate(c, rays, n, depth, fmt, out);
+  if (rc != RT_OK) return rc;
+  if (n == 0) {
+    if (st) *st = rt_radiance_stats{};
+    return RT_OK;
+  }
+  RT_TRY(c, hipSetDevice(c->device));
+  RadianceState &rs = c->radiance;
+  const size_t out_bytes = n * radiance_record(fmt);
+  const rt_ray *d_rays = rays;
+  void *d_out = out;
+  if (!on_device) {
+    if ((rc = grow(c, rs.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
+    if ((rc = grow(c, rs.out, out_bytes)) != RT_OK) return rc;
+    d_rays = rs.rays.get(), d_out = rs.out.get();
+    RT_TRY(c, hipMemcpyAsync(rs.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = rt_trace_radiance_async(c, d_rays, n, depth, fmt, d_out)) != RT_OK) return rc;
+  if (!on_device) RT_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  rt_radiance_stats tmp;
+  return rt_radiance_stats_get(c, st ? st : &tmp);
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {

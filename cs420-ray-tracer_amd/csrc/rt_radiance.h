@@ -1,0 +1,277 @@
+// Radiance queries (rt_trace_radiance): trace_ray (src/main.cpp:16-58) for rays
+// the caller supplies -- path_kernel's levels (rt_paths.h: the closest hit, the
+// whole of Scene::in_shadow per light, the reflection decision and its ray) with
+// Scene::shade (scene.h:89-121) formed at every hit and the levels composited
+// innermost first, as trace_wave unwinds them (rt_kernel.hip).  The Phong
+// arithmetic is shade_hit's, operand for operand, so a camera ray's radiance is
+// the render's RT_FB_F64X3 value of its pixel.  Included only by rt_kernel.hip,
+// after rt_paths.h.
+#pragma once
+
+#include "rt_paths.h"
+
+namespace rtk {
+
+// The radiance query's own counter block: the path counters, then the channels
+// RT_FB_RGB8 stored as 0 because they were negative.
+enum { kRcNegative = kPathCounters, kRadianceCounters };
+static_assert(kRadianceCounters <= kShardStride, "a shard holds the radiance counters");
+
+struct RadianceArgs {
+  PathArgs q;       // scene, rays, depth, region, walks and counters as a path launch's; verts / surf unused
+  D3 amb;           // scene.h:91
+  int fmt;          // RT_FB_*: the record written per ray
+  void *out;        // [nrays] records, ray i at record i
+  StackEnt *stack;  // [depth - 1][sstride]: the reflection stack of the launch's lane slots
+  unsigned sstride; // lane slots of the launch: gridDim.x * 64
+  int park_off;     // byte offset in dynamic LDS of the wave's parked colours, D3[64]
+};
+
+// path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
+// over the batch, a wave-uniform level loop in which an ended lane (or one past
+// the end of the batch) stays in every sweep with act = false, and the same
+// fast / slow split per segment and per shadow ray.  What it adds:
+//  * col, Scene::shade's accumulator: per unshadowed light the Phong terms of
+//    shade_hit's light loop.  The wide form (hit lanes at most half the wave)
+//    has the helper lane compute the term of its (hit lane, light) pair from the
+//    owner's hit point, normal, view direction and sphere, and the owner add
+//    its lights' terms in file order: the same bits as the lane-per-ray loop.
+//  * the reflection stack.  A level that spawns stores {shade*(1-refl), refl}
+//    at stack[slot + level * sstride], slot = blockIdx.x * 64 + lane: a slot
+//    belongs to a lane of the launch, not to a ray, and is reused on every
+//    grid-stride trip (a lane reads only what it wrote on this trip).
+//  * the parked colour.  The colour of the level at which a lane's chain ends
+//    (sky, shade, or shade*(1-refl) with no depth left) waits in LDS, 24 bytes
+//    per lane behind the walks' stacks, while the wave's other lanes go on, as
+//    trace_wave's kPark does: held in registers it cost 44 spilled VGPRs, not 28.
+//  * the store: one record per lane, consecutive lanes to consecutive records.
+// The format is switched at the store, after the level loop: it holds no
+// register where the pressure is, and one instantiation serves the three.
+// amdgpu_waves_per_eu(3), as path_kernel: left alone the allocator takes 201
+// VGPRs and no scratch, two waves per SIMD; held to the 168 of three waves it
+// spills 28 VGPRs (112 bytes of scratch per lane) and takes 14-20 % less time
+// ("Radiance").
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(const RadianceArgs a) {
+  const PathArgs &q = a.q;
+  const int lane = (int)(threadIdx.x & 63);
+  const long long n = q.nrays, step = (long long)gridDim.x * 64;
+  const unsigned slot = blockIdx.x * 64u + (unsigned)lane;
+  D3 *park = reinterpret_cast<D3 *>(rt_dyn_lds + a.park_off);
+  Work work;
+  unsigned c_rays = 0, c_seg = 0, c_hits = 0, c_shadow = 0, c_slow = 0, c_neg = 0;
+  const double2 *__restrict__ src = reinterpret_cast<const double2 *>(q.rays);
+  for (long long base = (long long)blockIdx.x * 64; base < n; base += step) {
+    const long long i = base + lane;
+    const bool act = i < n;
+    const long long ld = act ? i : n - 1;
+    const double2 r0 = src[ld * 4 + 0], r1 = src[ld * 4 + 1], r2 = src[ld * 4 + 2];
+    D3 o = mk(r0.x, r0.y, r1.x);
+    D3 d = normalized(mk(r1.y, r2.x, r2.y));  // Ray(o, d), ray.h:12: once
+    bool alive = act;
+    int key = -1;  // the sphere the ray leaves: groups the sweeps' lanes, changes no result
+    int lev = 0;   // stack entries this lane holds
+    for (int k = 0; k < q.depth && __ballot(alive) != 0; ++k) {
+      // ---- the closest hit of this level's ray (scene.h:41-61), as path_kernel
+      const bool fast = alive && q.accel != 0 && path_in_region(q, o, d);
+      const bool slow = alive && !fast;
+      double t_fast = kInf, t_slow = kInf;
+      int s_fast = -1, s_slow = -1;
+      if (__ballot(fast) != 0) s_fast = sweep_closest<true, false>(q.geo, q.rad, q.n, fast, o, d, key, q.bv, t_fast, work);
+      if (__ballot(slow) != 0) s_slow = sweep_closest<false>(q.geo, q.rad, q.n, slow, o, d, key, q.bv, t_slow, work);
+      const int sphere = alive ? (fast ? s_fast : s_slow) : -1;
+      const double t = alive ? (fast ? t_fast : t_slow) : kInf;
+      const bool hit = alive && sphere >= 0;
+      c_seg += alive ? 1u : 0u;
+      c_slow += slow ? 1u : 0u;
+      c_hits += hit ? 1u : 0u;
+      if (alive && !hit) {  // sky, main.cpp:26-30 (shade_hit)
+        const double st = 0.5 * (d.y + 1.0);
+        park[lane] = add(scale(mk(1.0, 1.0, 1.0), 1.0 - st), scale(mk(0.5, 0.7, 1.0), st));
+      }
+      const int hi = RT_CK(kCkSphere, hit ? sphere : 0, q.n > 0 ? q.n : 1);
+      const D3 hp = add(o, scale(d, t));  // main.cpp:32
+      D3 col;
+      {
+        const SphMat m0 = q.mat[hi];
+        col = mul(a.amb, mk(m0.cr, m0.cg, m0.cb));  // scene.h:91
+      }
+      D3 nrm = mk(0.0, 0.0, 0.0), view = nrm;
+      if (hit) {
+        const SphGeo sg = q.geo[hi];
+        nrm = normalized(sub(hp, mk(sg.cx, sg.cy, sg.cz)));  // sphere.h:62-64
+        view = normalized(sub(o, hp));                       // main.cpp:38
+      }
+      // ---- Scene::shade's light loop (scene.h:94-120): per light in file order the whole of
+      // in_shadow (path_kernel's query), then, if lit, the Phong terms with the same ldir
+      auto in_shadow = [&](bool need, D3 hq, D3 lp, D3 ldir, double dist, int gkey, bool one_light) {
+        const D3 so = add(hq, scale(ldir, kEps));
+        const D3 sd = renormalized(ldir);  // Ray() normalises the unit direction again
+        const bool sfast = need && q.accel != 0 && path_in_region(q, so, sd);
+        const bool sslow = need && !sfast;  // a light at the hit point among them: a NaN direction, never shadowed
+        bool occ = false;
+        const unsigned long long fm = __ballot(sfast);
+        if (fm != 0) {
+          const int f0 = __builtin_ctzll(fm);
+          const D3 P = one_light ? lp : mk(lane_bcast(so.x, f0), lane_bcast(so.y, f0), lane_bcast(so.z, f0));
+          occ = sweep_shadow<true>(q.geo, q.rad, q.n, sfast, so, sd, P, gkey, dist, q.bv, work);
+        }
+        if (__ballot(sslow) != 0) {
+          const bool os = sweep_shadow<false>(q.geo, q.rad, q.n, sslow, so, sd, so, gkey, dist, q.bv, work);
+          occ = sfast ? occ : os;
+        }
+        c_slow += sslow ? 1u : 0u;
+        return need && occ;
+      };
+      // one light's specular + diffuse for a lit point: shade_hit's terms, same operands and order
+      auto phong = [&](const SphMat &m, const LightD &L, D3 nq, D3 vq, D3 ldir) {
+        const double ndl = max0(dot(nq, ldir));
+        const D3 diffuse = scale(scale(mk(m.cr, m.cg, m.cb), 1.0 - m.refl), ndl);
+        const D3 nl2 = scale(ldir, -1.0);
+        const D3 rdir = sub(nl2, scale(scale(nq, 2.0), dot(nl2, nq)));  // reflect(), vec3.h:31-33
+        const double rdv = max0(dot(rdir, vq));
+        double spec = 0.0;  // pow(+0, y > 0) is +0 exactly (C99 F.10.4.4)
+        int ipow = 0;
+        if (!(rdv == 0.0 && m.shin > 0.0))
+          spec = int_pow_ok(rdv, m.shin, ipow) ? int_pow(rdv, ipow) : pow_call(rdv, m.shin);
+        const D3 specular = scale(scale(mk(L.cr, L.cg, L.cb), kSpec), spec);
+        return add(specular, diffuse);
+      };
+      const unsigned long long hm = __ballot(hit);
+      const int nh = __popcll(hm);
+      const int lpp = nh ? (64 / nh < q.nl ? 64 / nh : q.nl) : 0;  // lights per pass
+      if (q.nl >= 2 && lpp >= 2) {  // wave-uniform: the wide form, as shade_hit's kWide branch
+        const int rank = (int)__popcll(hm & ((1ull << lane) - 1ull));
+        for (int l0 = 0; l0 < q.nl; l0 += lpp) {  // lights l0 .. l0 + cnt - 1 in this pass
+          const int cnt = q.nl - l0 < lpp ? q.nl - l0 : lpp;
+          const bool helper = lane < nh * cnt;
+          const int r = helper ? lane / cnt : 0, lh = l0 + (helper ? lane - r * cnt : 0);
+          const int own = nth_set_bit(hm, r);  // the owner: the r-th hit lane
+          const D3 hq = mk(__shfl(hp.x, own, 64), __shfl(hp.y, own, 64), __shfl(hp.z, own, 64));
+          const int hq_i = RT_CK(kCkSphere, __shfl(hi, own, 64), q.n > 0 ? q.n : 1);
+          const LightD L = q.lights[lh];
+          const D3 lp = mk(L.px, L.py, L.pz);
+          const D3 to_light = sub(lp, hq);
+          const double dist = length(to_light);
+          const D3 ldir = normalized(to_light);
+          const bool occ = in_shadow(helper, hq, lp, ldir, dist, lh, false);  // lanes of one light sweep together
+          // the owner's normal and view direction, passed over after the sweeps (by every lane: a
+          // shuffle reads nothing from a lane that is switched off)
+          const D3 nq = mk(__shfl(nrm.x, own, 64), __shfl(nrm.y, own, 64), __shfl(nrm.z, own, 64));
+          const D3 vq = mk(__shfl(view.x, own, 64), __shfl(view.y, own, 64), __shfl(view.z, own, 64));
+          D3 term = mk(0.0, 0.0, 0.0);
+          const bool lit = helper && !occ;
+          if (lit) term = phong(q.mat[hq_i], L, nq, vq, ldir);
+          // each hit lane adds this pass's lights' terms in file order (scene.h:117)
+          const unsigned long long litm = __ballot(lit);
+          for (int l = 0; l < cnt; ++l) {
+            const int sl = hit ? rank * cnt + l : 0;
+            const D3 tl = mk(__shfl(term.x, sl, 64), __shfl(term.y, sl, 64), __shfl(term.z, sl, 64));
+            if (hit && ((litm >> sl) & 1ull)) col = add(tl, col);
+          }
+        }
+      } else if (hm != 0) {
+        for (int l = 0; l < q.nl; ++l) {
+          const LightD L = q.lights[l];
+          const D3 lp = mk(L.px, L.py, L.pz);
+          const D3 to_light = sub(lp, hp);
+          const double dist = length(to_light);
+          const D3 ldir = normalized(to_light);
+          const bool occ = in_shadow(hit, hp, lp, ldir, dist, hi, true);
+          if (hit && !occ) col = add(phong(q.mat[hi], L, nrm, view, ldir), col);  // scene.h:117
+        }
+      }
+      c_shadow += hit ? (unsigned)q.nl : 0u;
+      // ---- the reflection decision (main.cpp:43-55, shade_hit) and this level's stack entry; the
+      // material is read again here rather than held across the light loop
+      bool spawn = false;
+      if (hit) {
+        const double refl = q.mat[hi].refl;
+        if (refl > 0.0) {
+          const double w = 1.0 - refl;
+          const D3 A = mk(col.x * w, col.y * w, col.z * w);
+          spawn = q.depth - (k + 1) >= 1;
+          if (spawn) {
+            a.stack[RT_CK(kCkStack, slot + (unsigned)lev * a.sstride, (long long)(q.depth - 1) * a.sstride)] =
+                StackEnt{A.x, A.y, A.z, refl};
+            ++lev;
+          } else {
+            park[lane] = A;  // with no depth left trace_ray(depth 0) is black: A + (0,0,0)*refl == A
+          }
+        } else {
+          park[lane] = col;
+        }
+      }
+      // the reflection ray (main.cpp:45-48), shade_hit's operand order; formed by every lane, used
+      // by the lanes that spawn one (the others' chains have ended)
+      const D3 rd = sub(d, scale(scale(nrm, 2.0), dot(d, nrm)));
+      o = add(hp, scale(nrm, kEps));
+      d = renormalized(rd);
+      key = spawn ? hi : key;
+      alive = spawn;
+    }
+    D3 res = mk(0.0, 0.0, 0.0);
+    if (act) res = park[lane];
+    while (lev > 0) {  // unwind: shade*(1-refl) + reflected*refl, innermost first (trace_wave)
+      --lev;
+      const StackEnt e = a.stack[RT_CK(kCkStack, slot + (unsigned)lev * a.sstride, (long long)(q.depth - 1) * a.sstride)];
+      res = mk(e.ax + res.x * e.refl, e.ay + res.y * e.refl, e.az + res.z * e.refl);
+    }
+    c_rays += act ? 1u : 0u;
+    // ---- the record of ray i
+    if (a.fmt == RT_FB_RGB8) {
+      // quantised as write_ppm (main.cpp:85-87): a negative channel is stored as 0 and counted; a NaN
+      // is 1.0 to std::min(1.0, c), so 255 and not counted.  A whole wave's 64 records are 192 contiguous bytes from a dword boundary
+      // (base is a multiple of 64): lanes 0-47 store them as dwords assembled with two shuffles, as
+      // trace_tile's rows are; the batch's last, partial wave stores bytes.
+      unsigned v = 0;  // r | g << 8 | b << 16
+      if (act) {
+        const int q0 = quantize(res.x), q1 = quantize(res.y), q2 = quantize(res.z);
+        c_neg += (unsigned)((q0 < 0) + (q1 < 0) + (q2 < 0));
+        v = (unsigned)(q0 < 0 ? 0 : q0) | (unsigned)(q1 < 0 ? 0 : q1) << 8 | (unsigned)(q2 < 0 ? 0 : q2) << 16;
+      }
+      uint8_t *rec = static_cast<uint8_t *>(a.out) + (size_t)base * 3;
+      const bool packed = __ballot(act) == ~0ull && (reinterpret_cast<uintptr_t>(rec) & 3u) == 0;
+      const int p0 = (4 * lane) / 3;  // dword `lane` holds bytes 4 lane .. 4 lane + 3: records p0, p0 + 1
+      const unsigned v0 = __shfl(v, p0 < 63 ? p0 : 63, 64), v1 = __shfl(v, p0 + 1 < 63 ? p0 + 1 : 63, 64);
+      if (packed) {
+        if (lane < 48) {
+          const unsigned long long both = (unsigned long long)v0 | (unsigned long long)v1 << 24;
+          reinterpret_cast<unsigned *>(rec)[lane] = (unsigned)(both >> (8 * (4 * lane - 3 * p0)));
+        }
+      } else if (act) {
+        uint8_t *px = rec + lane * 3;
+        px[0] = (uint8_t)v;
+        px[1] = (uint8_t)(v >> 8);
+        px[2] = (uint8_t)(v >> 16);
+      }
+    } else if (act) {
+      if (a.fmt == RT_FB_F64X3) {
+        double *f = static_cast<double *>(a.out) + (size_t)i * 3;
+        f[0] = res.x;
+        f[1] = res.y;
+        f[2] = res.z;
+      } else {  // RT_FB_F32X3, converted as trace_tile's store converts
+        float *f = static_cast<float *>(a.out) + (size_t)i * 3;
+        f[0] = (float)res.x;
+        f[1] = (float)res.y;
+        f[2] = (float)res.z;
+      }
+    }
+  }
+  const unsigned long long s_rays = wave_sum(c_rays), s_seg = wave_sum(c_seg), s_hits = wave_sum(c_hits);
+  const unsigned long long s_shadow = wave_sum(c_shadow), s_slow = wave_sum(c_slow), s_neg = wave_sum(c_neg);
+  const unsigned long long s_exact = wave_sum64(work.exact), s_cull = wave_sum64(work.cull);
+  if (lane == 0) {
+    unsigned long long *cs = counter_shard(q.counters);
+    atomicAdd(cs + kPcRays, s_rays);
+    atomicAdd(cs + kPcSegments, s_seg);
+    atomicAdd(cs + kPcHits, s_hits);
+    atomicAdd(cs + kPcShadow, s_shadow);
+    atomicAdd(cs + kPcExact, s_exact);
+    atomicAdd(cs + kPcCull, s_cull);
+    atomicAdd(cs + kPcUnaccel, s_slow);
+    atomicAdd(cs + kRcNegative, s_neg);
+  }
+}
+
+}  // namespace rtk

@@ -15,6 +15,7 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   in_shadow (any hit)    include/scene.h:65-86           -> Renderer.trace_rays (RT_QUERY_OCCLUDED)
   Camera::get_ray        include/camera.h:17-25          -> Renderer.camera_rays
   trace_ray's skeleton   src/main.cpp:16-58              -> Renderer.trace_paths (hits, shadow masks, reflections)
+  trace_ray              src/main.cpp:16-58              -> Renderer.trace_radiance (colours of the caller's rays)
 """
 from __future__ import annotations
 
@@ -143,6 +144,16 @@ class rt_path_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# Radiance queries (rt_trace_radiance): the launch's counts.
+class rt_radiance_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("segments", C.c_uint64), ("hits", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("tests_exact", C.c_uint64), ("tests_cull", C.c_uint64), ("unaccelerated", C.c_uint64),
+                ("negative_clamped", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 RT_PATH_MAX_LIGHTS = 64
 RT_VERTEX_TRACED, RT_VERTEX_REFLECTS = 1, 2
 # numpy views of rt_vertex / rt_surface records (Renderer.trace_paths); built on first use
@@ -204,6 +215,10 @@ SIGNATURES = {
     "rt_trace_paths_async": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "rt_trace_paths": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, C.c_int, C.POINTER(rt_path_stats)]),
     "rt_path_stats_get": (C.c_int, [_P, C.POINTER(rt_path_stats)]),
+    "rt_trace_radiance_async": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P]),
+    "rt_trace_radiance": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, C.c_int,
+                                    C.POINTER(rt_radiance_stats)]),
+    "rt_radiance_stats_get": (C.c_int, [_P, C.POINTER(rt_radiance_stats)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -249,7 +264,7 @@ COMPAT_SIGNATURES = {
     "rt_compat_status": (C.c_int, []),
 }
 
-# framebuffer formats of rt_render_tile (rt_hip.h)
+# framebuffer formats of rt_render_tile and record formats of rt_trace_radiance (rt_hip.h)
 RT_FB_RGB8, RT_FB_F32X3, RT_FB_F64X3 = 0, 1, 2
 
 _libs = {}
@@ -551,6 +566,41 @@ class Renderer:
         """rt_path_stats_get: waits for the stream; the most recent path launch."""
         st = rt_path_stats()
         _check(self._L.rt_path_stats_get(self._ctx, C.byref(st)), "rt_path_stats_get", self._ctx, L=self._L)
+        return st
+
+    def trace_radiance(self, origins, directions, depth: int, fmt: int = RT_FB_F64X3):
+        """rt_trace_radiance from host memory: trace_ray's colour of Ray(origins[i], directions[i])
+        (numpy [n, 3]; any direction length) at `depth`.  Returns (colours, stats): a numpy [n, 3]
+        array of the format's dtype (float64 for RT_FB_F64X3, float32 for RT_FB_F32X3, uint8 for
+        RT_FB_RGB8), ray i in row i, and the launch's rt_radiance_stats."""
+        import numpy as np
+
+        o = np.asarray(origins, np.float64).reshape(-1, 3)
+        d = np.asarray(directions, np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"{n} origins, {d.shape[0]} directions")
+        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.float64)
+        out = np.zeros((n, 3), dtype)
+        st = rt_radiance_stats()
+        _check(self._L.rt_trace_radiance(self._ctx, C.c_void_p(rays.ctypes.data), n, depth, fmt,
+                                         C.c_void_p(out.ctypes.data), 0, C.byref(st)),
+               "rt_trace_radiance", self._ctx, L=self._L)
+        return out, st
+
+    def trace_radiance_device(self, rays_ptr: int, n: int, depth: int, fmt: int, out_ptr: int):
+        """rt_trace_radiance_async: n rt_ray records at rays_ptr, n packed records of `fmt` written
+        at out_ptr (device memory, 16-byte aligned), enqueued on the context's stream."""
+        _check(self._L.rt_trace_radiance_async(self._ctx, C.c_void_p(rays_ptr), n, depth, fmt, C.c_void_p(out_ptr)),
+               "rt_trace_radiance_async", self._ctx, L=self._L)
+
+    def radiance_stats(self) -> rt_radiance_stats:
+        """rt_radiance_stats_get: waits for the stream; the most recent radiance launch."""
+        st = rt_radiance_stats()
+        _check(self._L.rt_radiance_stats_get(self._ctx, C.byref(st)), "rt_radiance_stats_get", self._ctx, L=self._L)
         return st
 
     def close(self):

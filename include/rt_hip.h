@@ -45,6 +45,8 @@
  *                                      the closest hit, Scene::in_shadow include/scene.h:65-86 per light as a
  *                                      bit mask, Sphere::normal_at include/sphere.h:62-64 and the reflection
  *                                      ray main.cpp:43-48, for rays the caller supplies
+ *   rt_trace_radiance / rt_trace_radiance_async / rt_radiance_stats_get
+ *                                   <- trace_ray, src/main.cpp:16-58, for rays the caller supplies
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -52,7 +54,7 @@
  * (the reference's CUDA_CHECK -> exit(1), src/main_gpu.cu:27-35, is not kept).
  * Threading: one rt_ctx per device per host thread; distinct contexts are
  * independent and may be used concurrently.
- * Streams: all device work of a context (renders, ray and path queries, rt_unpermute_rows) is
+ * Streams: all device work of a context (renders, ray, path and radiance queries, rt_unpermute_rows) is
  * enqueued on ONE stream, the context's current stream, and is ordered only
  * on it.  The context's own stream (the default) is a BLOCKING stream: it is
  * ordered with the legacy NULL stream, so device buffers a caller fills or
@@ -78,7 +80,8 @@ extern "C" {
                                    under 12 as well (new symbols only: nothing existing changed),
                                    and so were rt_group_render_frames, the ray queries (rt_trace_rays,
                                    rt_trace_rays_async, rt_trace_stats, rt_camera_rays) and the path queries
-                                   (rt_trace_paths, rt_trace_paths_async, rt_path_stats_get) */
+                                   (rt_trace_paths, rt_trace_paths_async, rt_path_stats_get) and the radiance
+                                   queries (rt_trace_radiance, rt_trace_radiance_async, rt_radiance_stats_get) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -336,9 +339,9 @@ int rt_unpermute_rows(rt_ctx *ctx, const uint8_t *gathered_device, uint8_t *imag
  * The questions the render loop asks the scene, asked directly: "which sphere
  * does this ray hit, and where" (Scene::find_intersection, scene.h:41-61) and
  * "is anything between these two points" (the any-hit half of Scene::in_shadow,
- * scene.h:65-86), in the reference's fp64 semantics, bit for bit.  There is no
- * radiance query: per-ray colours could not be pinned to the reference; the
- * path queries below return what a caller shades from.
+ * scene.h:65-86), in the reference's fp64 semantics, bit for bit.  The path
+ * queries below return a ray's whole reflection path, the radiance queries
+ * after them its colour.
  * Queries are launches of their own: they have their own events and counters,
  * are not listed by rt_kernel_times, do not change what rt_render_stats or
  * rt_get_info report, and use none of the render scratch. */
@@ -393,9 +396,9 @@ int rt_camera_rays(rt_ctx *ctx, const rt_camera *cam, int width, int height, con
 /* ---- path queries: reflection paths and shadow masks for the caller's rays --
  * Everything trace_ray (src/main.cpp:16-58) does for a ray except the colour arithmetic: per reflection
  * level the closest hit, per light whether Scene::in_shadow says shadowed, and the reflection decision --
- * the geometric skeleton of the ray's path, in the reference's fp64 semantics, bit for bit.  The library
- * still returns no colour; a caller shades from these records with the reference's Phong
- * or with a model of its own. */
+ * the geometric skeleton of the ray's path, in the reference's fp64 semantics, bit for bit.  No colour is
+ * formed here: a caller shades from these records with a model of its own, or asks
+ * rt_trace_radiance below for the reference's. */
 #define RT_PATH_MAX_LIGHTS 64            /* bits of rt_vertex.shadowed */
 #define RT_VERTEX_TRACED   1             /* this level's ray was traced */
 #define RT_VERTEX_REFLECTS 2             /* a reflection ray was spawned: the next level is traced */
@@ -452,6 +455,56 @@ int rt_trace_paths(rt_ctx *ctx, const rt_ray *rays, size_t n, int depth, rt_vert
                    rt_surface *surf /* nullable */, int on_device, rt_path_stats *stats /* nullable */);
 /* Waits for the stream; the counts and time of the most recent path launch (zeros before the first). */
 int rt_path_stats_get(rt_ctx *ctx, rt_path_stats *stats);
+
+/* ---- radiance queries: trace_ray's colour for the caller's rays -------------
+ * The last thing trace_ray (src/main.cpp:16-58) does with a ray: the path above, shaded at every hit by
+ * Scene::shade (include/scene.h:89-121) and composited -- a renderer for ray sets of the caller's own
+ * (fisheye or panoramic cameras, depth of field, supersampling patterns, light probes). */
+typedef struct rt_radiance_stats {       /* 72 bytes */
+    uint64_t rays, segments, hits, shadow_rays;   /* as rt_path_stats */
+    uint64_t tests_exact, tests_cull, unaccelerated;
+    uint64_t negative_clamped;           /* RT_FB_RGB8 only, as rt_stats.negative_clamped */
+    double   kernel_ms;                  /* HIP-event time of the radiance kernel */
+} rt_radiance_stats;
+/* out[i] = trace_ray(Ray(origin_i, direction_i), scene, depth): the direction normalised once as
+   rt_trace_rays does; rt_ray.tmax and reserved are ignored; depth is trace_ray's, 1..RT_MAX_DEPTH.
+   Per level: the closest hit exactly as RT_QUERY_CLOSEST; a miss gets the sky (main.cpp:28-29); a hit gets
+   Scene::shade over ALL lights in file order, each with the whole of in_shadow as rt_trace_paths describes
+   it -- there is no RT_PATH_MAX_LIGHTS limit, because there is no mask.  The reflection decision and the
+   reflection ray are rt_trace_paths'; the levels are composited innermost first,
+   shade*(1-refl) + below*refl (main.cpp:54).
+   The arithmetic is the render kernels' own -- the Phong terms and specular + diffuse + colour in their
+   operand order, pow(+0, shininess > 0) skipped, the specular power by the render's routines, no
+   contraction -- so the radiance of a camera ray is the RT_FB_F64X3 value rt_render_tile stores for its
+   pixel.  The note on RT_FB_F64X3 applies: numerically the reference's, but a zero channel may differ in
+   sign (a hit of reflectivity > 1 with no depth left stores col*(1-refl) = -0.0).
+   A zero, NaN or infinite ray is a traced miss at level 0: its sky colour comes from the NaN direction.
+   It is never an error.
+   fb_format selects the packed record, ray i at record i: RT_FB_F64X3 3 doubles; RT_FB_F32X3 3 floats,
+   converted as the render's F32X3 store converts; RT_FB_RGB8 3 bytes through write_ppm's quantiser
+   (main.cpp:85-87), a negative value stored as 0 and counted in negative_clamped as rt_stats documents; a
+   NaN channel passes std::min(1.0, c) as 1.0, so it is stored as 255, the reference's own byte, and not
+   counted.  There is no row flip in any format: rt_camera_rays emits PPM order,
+   so rt_camera_rays + rt_trace_radiance(RT_FB_RGB8) writes rt_render's bytes.
+   rt_set_antialias does not apply (the samples are the caller's rays).  The acceleration rule per segment
+   and per shadow ray is rt_trace_paths' (`unaccelerated`); rt_set_culling(ctx, 0) sends every query
+   through the every-sphere sweep.  Light, camera and sphere grids are not used.
+   rays_device / out_device: memory of the context's device, 16-byte aligned, n records each.
+   Errors, before any HIP call: n == 0 is RT_OK and a no-op; n > 2^31-1, a NULL rays / out with n > 0,
+   depth < 1, an unknown fb_format or a misaligned device pointer is RT_ERR_INVALID_ARG;
+   depth > RT_MAX_DEPTH is RT_ERR_DEPTH; no uploaded scene is RT_ERR_NO_SCENE.
+   Radiance launches have their own events, counters and scratch (a reflection stack bounded by the
+   launch's grid, not by n): they are not listed by rt_kernel_times, change nothing that rt_render_stats,
+   rt_get_info, rt_trace_stats or rt_path_stats_get report, and use none of the render scratch.
+   Asynchronous on the context's current stream, ordered as every other launch of the context. */
+int rt_trace_radiance_async(rt_ctx *ctx, const rt_ray *rays_device, size_t n, int depth, int fb_format,
+                            void *out_device);
+/* Synchronous; rays / out in host memory (staged through grow-only buffers of the context), or
+   (on_device = 1) device memory as above; stats may be NULL. */
+int rt_trace_radiance(rt_ctx *ctx, const rt_ray *rays, size_t n, int depth, int fb_format, void *out,
+                      int on_device, rt_radiance_stats *stats /* nullable */);
+/* Waits for the stream; the counts and time of the most recent radiance launch (zeros before the first). */
+int rt_radiance_stats_get(rt_ctx *ctx, rt_radiance_stats *stats);
 
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
