@@ -24,6 +24,9 @@
 // launches of at most B frames (default: the library's largest), into memory of
 // the first device; the time line is the whole sequence's, one more line gives
 // the frames and the time per frame, and the LAST frame is the output image.
+// --supersample N (1..8, one device only: not with --gpus, --devices or -a):
+// N x N samples per pixel at the offsets (a/N, b/N), box-filtered, through
+// rt_render_samples; --supersample 2 writes the bytes of -a.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -54,17 +57,20 @@ struct Opts {
   int samples = 1;
   std::vector<int> devices;  // --devices LIST: the pass renders through rt_group_*
   int frames = -1, batch = -1;  // --frames N [--batch B]: a sequence per pass (rt_group_render_frames); -1: not given
+  int supersample = 0;  // --supersample N: N x N samples per pixel through rt_render_samples; 0: not given
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
-               "usage: %s [--openmp] [-a] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
+               "usage: %s [--openmp] [-a | --supersample N] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
                "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
                "          [--json] [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
                "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
                "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
-               "                  sequence and writes the last; --batch B (0..%d, 0 = %d): frames per launch\n",
+               "                  sequence and writes the last; --batch B (0..%d, 0 = %d): frames per launch\n"
+               "  --supersample N N x N box-filtered samples per pixel (1..8); one device: not with --gpus,\n"
+               "                  --devices or -a\n",
                argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
   return 2;
 }
@@ -118,6 +124,35 @@ int render_single(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8
   res.primary = st.rays_primary;
   res.shadow = st.rays_shadow;
   res.reflect = st.rays_reflect;
+  res.negative = st.negative_clamped;
+  rt_destroy(ctx);
+  return 0;
+}
+
+// --supersample N: the full frame through rt_render_samples, N x N samples per pixel at (a/N, b/N), a fastest.
+int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
+  const int N = o.supersample;
+  std::vector<double> offsets;
+  for (int b = 0; b < N; b++)
+    for (int a = 0; a < N; a++) {
+      offsets.push_back((double)a / N);
+      offsets.push_back((double)b / N);
+    }
+  rt_ctx *ctx = nullptr;
+  CK(rt_create(o.device, &ctx));
+  CK(rt_upload_scene(ctx, &sc));
+  rt_radiance_stats st{};
+  for (int it = 0; it < o.repeat; it++) {
+    auto t0 = std::chrono::high_resolution_clock::now();
+    CK(rt_render_samples(ctx, &cam, o.width, o.height, o.depth, nullptr, offsets.data(), N * N, nullptr, RT_FB_RGB8,
+                         img, 0, 0, &st));
+    auto t1 = std::chrono::high_resolution_clock::now();
+    res.wall_s = std::chrono::duration<double>(t1 - t0).count();
+  }
+  res.kernel_ms = st.kernel_ms;
+  res.primary = st.rays;
+  res.shadow = st.shadow_rays;
+  res.reflect = st.segments - st.rays;
   res.negative = st.negative_clamped;
   rt_destroy(ctx);
   return 0;
@@ -278,7 +313,8 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
   (void)madvise(img.get(), img_cap, MADV_HUGEPAGE);
   std::memset(img.get(), 0, img_cap);
   Result res;
-  int rc = !o.devices.empty()               ? render_group(o, sc, cam, img.get(), res)
+  int rc = o.supersample                    ? render_supersampled(o, sc, cam, img.get(), res)
+           : !o.devices.empty()             ? render_group(o, sc, cam, img.get(), res)
            : (o.gpus > 1 || o.force_gather) ? render_multi(o, sc, cam, img.get(), res)
                                             : render_single(o, sc, cam, img.get(), res);
   if (rc) return rc;
@@ -316,6 +352,7 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
 
 int main(int argc, char **argv) {
   Opts o;
+  bool gpus_given = false;
   std::string base = argv[0];
   size_t slash = base.find_last_of('/');
   if (slash != std::string::npos) base = base.substr(slash + 1);
@@ -332,7 +369,7 @@ int main(int argc, char **argv) {
     else if (a == "--width") { if (!next(o.width)) return usage(argv[0]); }
     else if (a == "--height") { if (!next(o.height)) return usage(argv[0]); }
     else if (a == "--depth") { if (!next(o.depth)) return usage(argv[0]); }
-    else if (a == "--gpus") { if (!next(o.gpus)) return usage(argv[0]); }
+    else if (a == "--gpus") { if (!next(o.gpus)) return usage(argv[0]); gpus_given = true; }
     else if (a == "--device") { if (!next(o.device)) return usage(argv[0]); }
     else if (a == "--devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.devices)) return usage(argv[0]); }
     else if (a == "--frames") { if (!next(o.frames) || o.frames < 1) return usage(argv[0]); }
@@ -342,12 +379,14 @@ int main(int argc, char **argv) {
     else if (a == "--p6") o.p6 = true;
     else if (a == "--force-gather") o.force_gather = true;
     else if (a == "-a") o.samples = 4;
+    else if (a == "--supersample") { if (!next(o.supersample) || o.supersample < 1 || o.supersample > 8) return usage(argv[0]); }
     else if (a == "--json") o.json = true;
     else if (a == "-h" || a == "--help") return usage(argv[0]);
     else o.scene = a;  // any other argument is the scene path, as main.cpp:103-110
   }
   if (o.width <= 0 || o.height <= 0 || o.gpus < 1 || o.repeat < 1) return usage(argv[0]);
   if (!o.devices.empty() && (o.gpus > 1 || o.force_gather)) return usage(argv[0]);
+  if (o.supersample && (gpus_given || !o.devices.empty() || o.force_gather || o.samples != 1)) return usage(argv[0]);
   if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116

@@ -3678,11 +3678,17 @@ static int radiance_state(rt_ctx *c) {
 // larger budget ("Radiance").
 constexpr size_t kRadianceStackBudget = 256u << 20;
 
-int rt_trace_radiance_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out) {
-  int rc = radiance_validate(c, rays, n, depth, fmt, out);
-  if (rc != RT_OK) return rc;
-  if (n == 0) return RT_OK;
-  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+// What a resolving launch adds to a radiance launch (rt_trace_radiance_resolve).
+struct ResolveSpec {
+  int samples;
+  const double *weights;  // host, samples of them; nullptr: the box filter
+};
+
+// One radiance launch, validated by its entry point: n records from n rays (rv == nullptr,
+// radiance_kernel<false>) or from n * rv->samples rays (radiance_kernel<true>).
+static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out,
+                           const ResolveSpec *rv) {
+  int rc;
   RT_TRY(c, hipSetDevice(c->device));
   if ((rc = radiance_state(c)) != RT_OK) return rc;
   const Scene &sc = c->scene;
@@ -3724,11 +3730,30 @@ int rt_trace_radiance_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, 
   a.sstride = (unsigned)grid * 64u;
   RT_TRY(c, hipMemsetAsync(rs.ctr.get(), 0, rs.ctr.bytes(), c->stream));
   RT_TRY(c, hipEventRecord(rs.ev0, c->stream));
-  hipLaunchKernelGGL(radiance_kernel, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
+  if (!rv) {
+    hipLaunchKernelGGL(radiance_kernel<false>, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
+  } else {
+    ResolveArgs ra{};
+    ra.r = a;
+    ra.samples = rv->samples;
+    ra.mode = rv->weights ? kResolveWeighted : rv->samples == 1 ? kResolveSingle : kResolveBox;
+    lds += 64 * sizeof(D3);  // the wave's accumulators, right behind its parked colours
+    ra.inv = 1.0 / (double)rv->samples;
+    for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
+    hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
+  }
   RT_TRY(c, hipGetLastError());
   RT_TRY(c, hipEventRecord(rs.ev1, c->stream));
   rs.launched = true;
   return RT_OK;
+}
+
+int rt_trace_radiance_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out) {
+  int rc = radiance_validate(c, rays, n, depth, fmt, out);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+  return radiance_launch(c, rays, n, depth, fmt, out, nullptr);
 }
 
 int rt_radiance_stats_get(rt_ctx *c, rt_radiance_stats *st) {
@@ -3780,6 +3805,154 @@ int rt_trace_radiance(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fm
   if (!on_device) RT_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
   rt_radiance_stats tmp;
   return rt_radiance_stats_get(c, st ? st : &tmp);
+}
+
+// ---- multi-sample pixels (rt_radiance.h, kResolve) --------------------------
+// The checks rt_camera_sample_rays and rt_render_samples share, before any HIP call.
+static int sample_rays_validate(const rt_ctx *c, const rt_camera *cam, int W, int H, const Rows &r,
+                                const double *offsets, int samples) {
+  if (!c || !cam || !offsets || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
+  if (samples < 1 || samples > RT_MAX_SAMPLES) return RT_ERR_INVALID_ARG;
+  if (r.band < 1 || r.stride < 1 || r.first < 0 || r.count < 0) return RT_ERR_INVALID_ARG;
+  return RT_OK;
+}
+
+// The rays of output rows k_first .. k_first + nrows - 1 of `r`, nrows * W * samples <= 2^31-1 of them.
+static int sample_rays_launch(rt_ctx *c, const rt_camera *cam, int W, int H, const Rows &r, int k_first, int nrows,
+                              const double *offsets, int samples, rt_ray *rays) {
+  SampleOffsets off{};
+  std::memcpy(off.xy, offsets, (size_t)samples * 2 * sizeof(double));  // by value: the caller's array is free on return
+  const long long total = (long long)nrows * W * samples;
+  const unsigned grid = (unsigned)((total + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(camera_sample_rays_kernel, dim3(grid), dim3(kBlock), 0, c->stream, to_cam(*cam), W, H, r, k_first,
+                     nrows, samples, off, rays);
+  RT_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_camera_sample_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows *rows, const double *offsets,
+                          int samples, rt_ray *rays) {
+  if (!rays || (reinterpret_cast<uintptr_t>(rays) & 15u)) return RT_ERR_INVALID_ARG;
+  const Rows r = to_rows(rows, H);
+  const int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
+  if (rc != RT_OK) return rc;
+  const long long total = (long long)r.count * W * samples;  // < 2^31 * 2^31 * 2^6
+  if (total > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (total == 0) return RT_OK;
+  RT_TRY(c, hipSetDevice(c->device));
+  return sample_rays_launch(c, cam, W, H, r, 0, r.count, offsets, samples, rays);
+}
+
+// The checks of the resolving entry points, before any HIP call: rt_trace_radiance's, and the sample count.
+static int resolve_validate(const rt_ctx *c, const void *rays, size_t n, int samples, int depth, int fmt,
+                            const void *out) {
+  if (!c || samples < 1 || samples > RT_MAX_SAMPLES) return RT_ERR_INVALID_ARG;
+  if (n > (size_t)INT32_MAX / (size_t)samples) return RT_ERR_INVALID_ARG;
+  return radiance_validate(c, rays, n, depth, fmt, out);
+}
+
+int rt_trace_radiance_resolve_async(rt_ctx *c, const rt_ray *rays, size_t n, int samples, const double *weights,
+                                    int depth, int fmt, void *out) {
+  int rc = resolve_validate(c, rays, n, samples, depth, fmt, out);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+  const ResolveSpec rv{samples, weights};
+  return radiance_launch(c, rays, n, depth, fmt, out, &rv);
+}
+
+int rt_trace_radiance_resolve(rt_ctx *c, const rt_ray *rays, size_t n, int samples, const double *weights, int depth,
+                              int fmt, void *out, int on_device, rt_radiance_stats *st) {
+  int rc = resolve_validate(c, rays, n, samples, depth, fmt, out);
+  if (rc != RT_OK) return rc;
+  if (n == 0) {
+    if (st) *st = rt_radiance_stats{};
+    return RT_OK;
+  }
+  RT_TRY(c, hipSetDevice(c->device));
+  RadianceState &rs = c->radiance;
+  const size_t nrays = n * (size_t)samples, out_bytes = n * radiance_record(fmt);
+  const rt_ray *d_rays = rays;
+  void *d_out = out;
+  if (!on_device) {
+    if ((rc = grow(c, rs.rays, nrays * sizeof(rt_ray))) != RT_OK) return rc;
+    if ((rc = grow(c, rs.out, out_bytes)) != RT_OK) return rc;
+    d_rays = rs.rays.get(), d_out = rs.out.get();
+    RT_TRY(c, hipMemcpyAsync(rs.rays.get(), rays, nrays * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = rt_trace_radiance_resolve_async(c, d_rays, n, samples, weights, depth, fmt, d_out)) != RT_OK) return rc;
+  if (!on_device) RT_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  rt_radiance_stats tmp;
+  return rt_radiance_stats_get(c, st ? st : &tmp);
+}
+
+// The ray buffer of rt_render_samples when the caller names no bound: a choice, 4 Mi rays
+// ("Samples", has the sweep).
+constexpr size_t kSampleRayBytes = 256u << 20;
+
+int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
+                      const double *offsets, int samples, const double *weights, int fmt, void *out, int on_device,
+                      size_t max_ray_bytes, rt_radiance_stats *st) {
+  const Rows r = to_rows(rows, H);
+  int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
+  if (rc != RT_OK) return rc;
+  const long long row_rays = (long long)W * samples;  // one output row: the smallest chunk
+  if (row_rays > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
+  const size_t rec = radiance_record(fmt);
+  if (depth < 1 || rec == 0) return RT_ERR_INVALID_ARG;
+  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  if (r.count == 0) {
+    if (st) *st = rt_radiance_stats{};
+    return RT_OK;
+  }
+  if (!out || (on_device && (reinterpret_cast<uintptr_t>(out) & 15u))) return RT_ERR_INVALID_ARG;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  RT_TRY(c, hipSetDevice(c->device));
+  // the rows of the image: a prefix of the output rows (y grows with k), the padding rows their suffix
+  auto row_y = [&](int k) {
+    return (long long)(k / r.band) * r.band * r.stride + (long long)r.first * r.band + (k % r.band);
+  };
+  int lo = 0, hi = r.count;  // the first k with row_y(k) >= H
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (row_y(mid) < H) lo = mid + 1; else hi = mid;
+  }
+  const int real = lo;
+  const size_t cap = max_ray_bytes ? max_ray_bytes : kSampleRayBytes;
+  long long chunk = std::max<long long>(1, (long long)(cap / ((size_t)row_rays * sizeof(rt_ray))));
+  chunk = std::min<long long>(chunk, (long long)INT32_MAX / row_rays);
+  RadianceState &rs = c->radiance;
+  uint8_t *dst = static_cast<uint8_t *>(out);
+  const ResolveSpec rv{samples, weights};
+  rt_radiance_stats sum{}, one{};
+  for (int k0 = 0; k0 < real; k0 += (int)chunk) {
+    const int nr = (int)std::min<long long>(chunk, real - k0);
+    const size_t npx = (size_t)nr * W, off = (size_t)k0 * W * rec;
+    if ((rc = grow(c, rs.rays, npx * samples * sizeof(rt_ray))) != RT_OK) return rc;
+    if (!on_device && (rc = grow(c, rs.out, npx * rec)) != RT_OK) return rc;
+    if ((rc = sample_rays_launch(c, cam, W, H, r, k0, nr, offsets, samples, rs.rays.get())) != RT_OK) return rc;
+    // a chunk's records begin where the previous chunk's end: aligned as the format, not to 16 bytes (the
+    // kernel's packed RGB8 store tests the alignment it needs)
+    void *d_out = on_device ? static_cast<void *>(dst + off) : static_cast<void *>(rs.out.get());
+    if ((rc = radiance_launch(c, rs.rays.get(), npx, depth, fmt, d_out, &rv)) != RT_OK) return rc;
+    if (!on_device) RT_TRY(c, hipMemcpyAsync(dst + off, d_out, npx * rec, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = rt_radiance_stats_get(c, &one)) != RT_OK) return rc;
+    sum.rays += one.rays, sum.segments += one.segments, sum.hits += one.hits, sum.shadow_rays += one.shadow_rays;
+    sum.tests_exact += one.tests_exact, sum.tests_cull += one.tests_cull, sum.unaccelerated += one.unaccelerated;
+    sum.negative_clamped += one.negative_clamped, sum.kernel_ms += one.kernel_ms;
+  }
+  // padding rows: not traced, not counted, zero bytes
+  const size_t pad_off = (size_t)real * W * rec, pad = (size_t)(r.count - real) * W * rec;
+  if (pad) {
+    if (on_device) {
+      RT_TRY(c, hipMemsetAsync(dst + pad_off, 0, pad, c->stream));
+      RT_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+      std::memset(dst + pad_off, 0, pad);
+    }
+  }
+  if (st) *st = sum;
+  return RT_OK;
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {

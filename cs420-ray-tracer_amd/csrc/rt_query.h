@@ -128,4 +128,39 @@ __global__ __launch_bounds__(kBlock) void camera_rays_kernel(const Cam cam, int 
   dst[3] = make_double2(__builtin_inf(), 0.0);
 }
 
+// rt_camera_sample_rays: camera_rays_kernel for a caller's sample pattern.  The
+// ray of output row k_first + k, column x, sample s is out[(k*W + x)*S + s]: the
+// camera position and normalized(camera_dir(x + ox_s, j + oy_s)), trace_tile's
+// antialias arithmetic (the offset is added before the division by W-1 / H-1;
+// x + 0.0 == x, so one (0,0) sample gives camera_rays_kernel's records).  The
+// offsets travel in the kernel arguments: a lane reads its sample's pair from
+// the kernarg segment.  k_first / nrows select a run of the output rows of
+// `rows` (rt_render_samples traces them in chunks).  One thread per ray.
+struct SampleOffsets {
+  double xy[2 * RT_MAX_SAMPLES];
+};
+__global__ __launch_bounds__(kBlock) void camera_sample_rays_kernel(const Cam cam, int W, int H, const Rows rows,
+                                                                     int k_first, int nrows, int S,
+                                                                     const SampleOffsets off,
+                                                                     rt_ray *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long long)nrows * W * S) return;
+  const int s = (int)(i % S);
+  const long long p = i / S;
+  const int k = k_first + (int)(p / W), x = (int)(p % W);
+  const long long y = (long long)(k / rows.band) * rows.band * rows.stride + (long long)rows.first * rows.band +
+                      (k % rows.band);
+  double2 *dst = reinterpret_cast<double2 *>(out) + i * 4;
+  if (y >= H) {  // padding rows of a shard
+    dst[0] = dst[1] = dst[2] = dst[3] = make_double2(0.0, 0.0);
+    return;
+  }
+  const int j = H - 1 - (int)y;  // reference row (main.cpp:74)
+  const D3 d = normalized(camera_dir(cam, (double)x + off.xy[2 * s], (double)j + off.xy[2 * s + 1], W, H));
+  dst[0] = make_double2(cam.px, cam.py);
+  dst[1] = make_double2(cam.pz, d.x);
+  dst[2] = make_double2(d.y, d.z);
+  dst[3] = make_double2(__builtin_inf(), 0.0);
+}
+
 }  // namespace rtk

@@ -27,6 +27,27 @@ struct RadianceArgs {
   int park_off;     // byte offset in dynamic LDS of the wave's parked colours, D3[64]
 };
 
+// The resolving launch (rt_trace_radiance_resolve): q.nrays counts PIXELS, pixel p's samples are
+// the rays p*samples .. p*samples + samples - 1, and record p is the pixel's.  Everything here is
+// wave-uniform and read from the kernel arguments.
+enum { kResolveSingle = 0, kResolveBox, kResolveWeighted };
+struct ResolveArgs {
+  RadianceArgs r;
+  int samples;  // 1..RT_MAX_SAMPLES
+  int mode;     // kResolveSingle: the colour itself; kResolveBox: (0 + c_0 + ...) * inv; kResolveWeighted: 0 + c_0*w_0 + ...
+  double inv;   // 1.0 / samples, formed once on the host
+  double w[RT_MAX_SAMPLES];
+};
+static_assert(offsetof(ResolveArgs, r) == 0, "radiance_kernel reads a ResolveArgs' launch through its first member");
+template <bool kResolve>
+struct RadianceLaunch {
+  using Args = RadianceArgs;
+};
+template <>
+struct RadianceLaunch<true> {
+  using Args = ResolveArgs;
+};
+
 // path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
 // over the batch, a wave-uniform level loop in which an ended lane (or one past
 // the end of the batch) stays in every sweep with act = false, and the same
@@ -51,7 +72,22 @@ struct RadianceArgs {
 // VGPRs and no scratch, two waves per SIMD; held to the 168 of three waves it
 // spills 28 VGPRs (112 bytes of scratch per lane) and takes 14-20 % less time
 // ("Radiance").
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(const RadianceArgs a) {
+//
+// kResolve (rt_trace_radiance_resolve, DESIGN.md section 5b, "Samples"): one lane per PIXEL, and a
+// wave-uniform loop over the pixel's samples around the level loop, as trace_tile loops its samples
+// around trace_wave: the wave traces sample s of 64 consecutive pixels together, a sample's chain
+// unwinds before the next begins (the lane's stack slots are reused), and the samples are added in
+// order by construction.  The accumulator waits in LDS right behind the parked colours (park[64 +
+// lane]: the same address register, another offset), for the same reason; it is read and written
+// once per sample.  With kResolve false the do-while's condition is a constant and every `if
+// constexpr` is gone: rt_trace_radiance's instantiation compiles to the instructions it had before
+// the template.  Two details keep it so (each was tried the other way and moved the code): the
+// launch is read through a cast, not a helper returning a reference; a chain's colour `res` keeps
+// its scope and is copied to `pix` for the store.
+template <bool kResolve>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(
+    const typename RadianceLaunch<kResolve>::Args ka) {
+  const RadianceArgs &a = reinterpret_cast<const RadianceArgs &>(ka);  // ResolveArgs::r, at offset 0
   const PathArgs &q = a.q;
   const int lane = (int)(threadIdx.x & 63);
   const long long n = q.nrays, step = (long long)gridDim.x * 64;
@@ -64,7 +100,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
     const long long i = base + lane;
     const bool act = i < n;
     const long long ld = act ? i : n - 1;
-    const double2 r0 = src[ld * 4 + 0], r1 = src[ld * 4 + 1], r2 = src[ld * 4 + 2];
+    int nsamp = 1;
+    if constexpr (kResolve) {
+      nsamp = ka.samples;
+      if (ka.mode != kResolveSingle) park[64 + lane] = mk(0.0, 0.0, 0.0);
+    }
+    D3 pix;
+    int s = 0;
+    do {  // the pixel's samples; the body keeps the level loop's indentation
+    const long long ri = kResolve ? ld * nsamp + s : ld;
+    const double2 r0 = src[ri * 4 + 0], r1 = src[ri * 4 + 1], r2 = src[ri * 4 + 2];
     D3 o = mk(r0.x, r0.y, r1.x);
     D3 d = normalized(mk(r1.y, r2.x, r2.y));  // Ray(o, d), ray.h:12: once
     bool alive = act;
@@ -217,7 +262,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
       res = mk(e.ax + res.x * e.refl, e.ay + res.y * e.refl, e.az + res.z * e.refl);
     }
     c_rays += act ? 1u : 0u;
-    // ---- the record of ray i
+    if constexpr (kResolve) {
+      if (ka.mode != kResolveSingle) {  // acc = acc + c_s, or acc + c_s * w_s: the product rounded, then the sum
+        D3 *accp = park + 64 + lane;
+        const D3 v = ka.mode == kResolveWeighted ? scale(res, ka.w[s]) : res;
+        *accp = add(*accp, v);
+      }
+    }
+    pix = res;
+    } while (kResolve && ++s < nsamp);  // constant false without kResolve: no loop is emitted
+    if constexpr (kResolve) {
+      if (ka.mode != kResolveSingle) {
+        pix = park[64 + lane];
+        if (ka.mode == kResolveBox) pix = scale(pix, ka.inv);  // trace_tile's scale(acc, 0.25) for four samples
+      }
+    }
+    // ---- the record of ray i (kResolve: of pixel i)
     if (a.fmt == RT_FB_RGB8) {
       // quantised as write_ppm (main.cpp:85-87): a negative channel is stored as 0 and counted; a NaN
       // is 1.0 to std::min(1.0, c), so 255 and not counted.  A whole wave's 64 records are 192 contiguous bytes from a dword boundary
@@ -225,7 +285,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
       // trace_tile's rows are; the batch's last, partial wave stores bytes.
       unsigned v = 0;  // r | g << 8 | b << 16
       if (act) {
-        const int q0 = quantize(res.x), q1 = quantize(res.y), q2 = quantize(res.z);
+        const int q0 = quantize(pix.x), q1 = quantize(pix.y), q2 = quantize(pix.z);
         c_neg += (unsigned)((q0 < 0) + (q1 < 0) + (q2 < 0));
         v = (unsigned)(q0 < 0 ? 0 : q0) | (unsigned)(q1 < 0 ? 0 : q1) << 8 | (unsigned)(q2 < 0 ? 0 : q2) << 16;
       }
@@ -247,14 +307,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
     } else if (act) {
       if (a.fmt == RT_FB_F64X3) {
         double *f = static_cast<double *>(a.out) + (size_t)i * 3;
-        f[0] = res.x;
-        f[1] = res.y;
-        f[2] = res.z;
+        f[0] = pix.x;
+        f[1] = pix.y;
+        f[2] = pix.z;
       } else {  // RT_FB_F32X3, converted as trace_tile's store converts
         float *f = static_cast<float *>(a.out) + (size_t)i * 3;
-        f[0] = (float)res.x;
-        f[1] = (float)res.y;
-        f[2] = (float)res.z;
+        f[0] = (float)pix.x;
+        f[1] = (float)pix.y;
+        f[2] = (float)pix.z;
       }
     }
   }

@@ -16,6 +16,8 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   Camera::get_ray        include/camera.h:17-25          -> Renderer.camera_rays
   trace_ray's skeleton   src/main.cpp:16-58              -> Renderer.trace_paths (hits, shadow masks, reflections)
   trace_ray              src/main.cpp:16-58              -> Renderer.trace_radiance (colours of the caller's rays)
+  the `-a` sample loop   src/main_gpu.cu:249-333         -> Renderer.render_samples, camera_sample_rays,
+                                                            trace_radiance_resolve (a caller's pattern and weights)
 """
 from __future__ import annotations
 
@@ -219,6 +221,15 @@ SIGNATURES = {
     "rt_trace_radiance": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, C.c_int,
                                     C.POINTER(rt_radiance_stats)]),
     "rt_radiance_stats_get": (C.c_int, [_P, C.POINTER(rt_radiance_stats)]),
+    "rt_camera_sample_rays": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.POINTER(rt_rows),
+                                        C.POINTER(C.c_double), C.c_int, _P]),
+    "rt_trace_radiance_resolve_async": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                                  C.c_int, _P]),
+    "rt_trace_radiance_resolve": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                            _P, C.c_int, C.POINTER(rt_radiance_stats)]),
+    "rt_render_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(rt_rows),
+                                    C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int,
+                                    C.c_size_t, C.POINTER(rt_radiance_stats)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -603,6 +614,79 @@ class Renderer:
         _check(self._L.rt_radiance_stats_get(self._ctx, C.byref(st)), "rt_radiance_stats_get", self._ctx, L=self._L)
         return st
 
+    def camera_sample_rays(self, cam: rt_camera, width: int, height: int, rows: rt_rows | None, offsets,
+                           rays_ptr: int):
+        """rt_camera_sample_rays: len(offsets) rays per pixel ((ox, oy) pairs, e.g. grid_pattern(n)) as
+        rt_ray records at rays_ptr (device memory, rows.count * width * len(offsets) of them, a
+        pixel's samples consecutive), asynchronously."""
+        off, s = _doubles(offsets, 2)
+        _check(self._L.rt_camera_sample_rays(self._ctx, C.byref(cam), width, height,
+                                             C.byref(rows) if rows is not None else None, off, s,
+                                             C.c_void_p(rays_ptr)),
+               "rt_camera_sample_rays", self._ctx, L=self._L)
+
+    def trace_radiance_resolve(self, origins, directions, samples: int, depth: int, weights=None,
+                               fmt: int = RT_FB_F64X3):
+        """rt_trace_radiance_resolve from host memory: numpy [n_pixels * samples, 3] origins and
+        directions, pixel p's samples in rows p*samples .. p*samples + samples - 1; weights None (the
+        box filter) or `samples` doubles.  Returns (pixels, stats): a numpy [n_pixels, 3] array of
+        the format's dtype and the launch's rt_radiance_stats."""
+        import numpy as np
+
+        o = np.asarray(origins, np.float64).reshape(-1, 3)
+        d = np.asarray(directions, np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"{n} origins, {d.shape[0]} directions")
+        if samples >= 1 and n % samples:
+            raise ValueError(f"{n} rays are not a multiple of {samples} samples")
+        npix = n // samples if samples >= 1 else n
+        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
+        rays[:, 0:3] = o
+        rays[:, 3:6] = d
+        dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.float64)
+        out = np.zeros((npix, 3), dtype)
+        w = _sample_weights(weights, samples)
+        st = rt_radiance_stats()
+        _check(self._L.rt_trace_radiance_resolve(self._ctx, C.c_void_p(rays.ctypes.data), npix, samples, w, depth,
+                                                 fmt, C.c_void_p(out.ctypes.data), 0, C.byref(st)),
+               "rt_trace_radiance_resolve", self._ctx, L=self._L)
+        return out, st
+
+    def trace_radiance_resolve_device(self, rays_ptr: int, n_pixels: int, samples: int, depth: int, fmt: int,
+                                      out_ptr: int, weights=None):
+        """rt_trace_radiance_resolve_async: n_pixels * samples rt_ray records at rays_ptr, n_pixels
+        packed records of `fmt` written at out_ptr (device memory, 16-byte aligned), enqueued on
+        the context's stream."""
+        w = _sample_weights(weights, samples)
+        _check(self._L.rt_trace_radiance_resolve_async(self._ctx, C.c_void_p(rays_ptr), n_pixels, samples, w, depth,
+                                                       fmt, C.c_void_p(out_ptr)),
+               "rt_trace_radiance_resolve_async", self._ctx, L=self._L)
+
+    def render_samples(self, cam: rt_camera, width: int, height: int, depth: int, offsets, weights=None,
+                       rows: rt_rows | None = None, fmt: int = RT_FB_RGB8, out=None, out_on_device: bool = False,
+                       max_ray_bytes: int = 0):
+        """rt_render_samples: the pixels of `rows` (None = the full frame) in PPM row order, each
+        resolved from len(offsets) samples ((ox, oy) pairs; weights None = the box filter).  `out`:
+        None (a host numpy [count * width, 3] array of the format's dtype is made), a host buffer,
+        or with out_on_device a device buffer / pointer.  Returns (out, stats), the stats summed
+        over the call's chunks of at most max_ray_bytes of rays (0 = the library's default)."""
+        off, s = _doubles(offsets, 2)
+        w = _sample_weights(weights, s)
+        count = rows.count if rows is not None else height
+        if out is None:
+            import numpy as np
+
+            dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.uint8)
+            out = np.zeros((max(count, 0) * width, 3), dtype)
+        ptr = out if isinstance(out, int) else _addr(out)
+        st = rt_radiance_stats()
+        _check(self._L.rt_render_samples(self._ctx, C.byref(cam), width, height, depth,
+                                         C.byref(rows) if rows is not None else None, off, s, w, fmt,
+                                         C.c_void_p(ptr), int(out_on_device), max_ray_bytes, C.byref(st)),
+               "rt_render_samples", self._ctx, L=self._L)
+        return out, st
+
     def close(self):
         if self._ctx:
             self._L.rt_destroy(self._ctx)
@@ -705,6 +789,36 @@ class Group:
             self.close()
         except Exception:
             pass
+
+
+def grid_pattern(n: int) -> list[tuple[float, float]]:
+    """The n x n sample offsets (a/n, b/n), a fastest: what Renderer.camera_sample_rays and
+    render_samples take.  grid_pattern(2) is the antialias pattern (main_gpu.cu:253-256) exactly:
+    (0,0) (.5,0) (0,.5) (.5,.5)."""
+    if n < 1:
+        raise ValueError(f"grid_pattern({n})")
+    return [(a / n, b / n) for b in range(n) for a in range(n)]
+
+
+def _doubles(values, width: int):
+    """(ctypes double array, records): `values` flattened, `width` doubles per record."""
+    flat = []
+    for v in values:
+        flat.extend(v) if width > 1 else flat.append(v)
+    flat = [float(x) for x in flat]
+    if len(flat) % width:
+        raise ValueError(f"{len(flat)} values are not records of {width}")
+    return (C.c_double * max(1, len(flat)))(*flat), len(flat) // width
+
+
+def _sample_weights(weights, samples: int):
+    """The `weights` argument of the resolving calls: None (the box filter) or `samples` doubles."""
+    if weights is None:
+        return None
+    w, n = _doubles(weights, 1)
+    if n != samples:
+        raise ValueError(f"{n} weights for {samples} samples")
+    return w
 
 
 def _addr(buf) -> int:

@@ -47,6 +47,9 @@
  *                                      ray main.cpp:43-48, for rays the caller supplies
  *   rt_trace_radiance / rt_trace_radiance_async / rt_radiance_stats_get
  *                                   <- trace_ray, src/main.cpp:16-58, for rays the caller supplies
+ *   rt_camera_sample_rays / rt_trace_radiance_resolve / rt_trace_radiance_resolve_async / rt_render_samples
+ *                                   <- the four-sample loop of ray_gpu's `-a`, src/main_gpu.cu:249-333, for a
+ *                                      sample pattern and weights the caller supplies
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -81,7 +84,9 @@ extern "C" {
                                    and so were rt_group_render_frames, the ray queries (rt_trace_rays,
                                    rt_trace_rays_async, rt_trace_stats, rt_camera_rays) and the path queries
                                    (rt_trace_paths, rt_trace_paths_async, rt_path_stats_get) and the radiance
-                                   queries (rt_trace_radiance, rt_trace_radiance_async, rt_radiance_stats_get) */
+                                   queries (rt_trace_radiance, rt_trace_radiance_async, rt_radiance_stats_get) and the
+                                   multi-sample entries (rt_camera_sample_rays, rt_trace_radiance_resolve,
+                                   rt_trace_radiance_resolve_async, rt_render_samples) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -505,6 +510,79 @@ int rt_trace_radiance(rt_ctx *ctx, const rt_ray *rays, size_t n, int depth, int 
                       int on_device, rt_radiance_stats *stats /* nullable */);
 /* Waits for the stream; the counts and time of the most recent radiance launch (zeros before the first). */
 int rt_radiance_stats_get(rt_ctx *ctx, rt_radiance_stats *stats);
+
+/* ---- multi-sample pixels: a caller's sample pattern, resolved on the device --
+ * The `-a` mode of ray_gpu (src/main_gpu.cu:249-333: four samples per pixel, summed in order and scaled
+ * by 0.25) for any pattern of up to RT_MAX_SAMPLES samples and any weights, on the query side: nothing
+ * here touches a render kernel or rt_set_antialias. */
+#define RT_MAX_SAMPLES 64
+/* Replaces a host restatement of camera_dir for sub-pixel samples (rt_camera_rays emits one ray per pixel,
+   at its corner).  samples rays per pixel as rt_ray records in DEVICE memory (16-byte aligned,
+   rows->count * width * samples of them; rows = NULL means the full frame), pixel-major with a pixel's
+   samples consecutive: the ray of output row k, column x, sample s is rays[(k*width + x)*samples + s].
+   origin = cam->position; direction = normalized(camera_dir(cam, (double)x + ox_s, (double)j + oy_s, W, H)),
+   j = H-1-y and (ox_s, oy_s) = offsets_xy[2s], offsets_xy[2s+1]: the antialias arithmetic of the render
+   kernels (main_gpu.cu:253-256), the offset added to (x, j) BEFORE the division by W-1 and H-1;
+   tmax = +inf, reserved = 0.  Padding rows (y >= H) get all-zero rays.  With samples = 1 and the offset
+   (0, 0) the records are bit-identical to rt_camera_rays' (x + 0.0 == x).
+   offsets_xy is HOST memory, 2*samples doubles, read during the call and passed to the kernel by value: it
+   may be freed on return.  Any double is allowed: a non-finite offset gives a NaN ray, which the queries
+   treat as a miss; it is never an error.  Needs no scene.  Asynchronous on the context's stream.
+   Errors, before any HIP call, all RT_ERR_INVALID_ARG: samples outside 1..RT_MAX_SAMPLES; a NULL
+   offsets_xy, cam or rays_device; a misaligned rays_device; rows->count * width * samples > 2^31-1. */
+int rt_camera_sample_rays(rt_ctx *ctx, const rt_camera *cam, int width, int height, const rt_rows *rows,
+                          const double *offsets_xy /* host, 2*samples doubles */, int samples,
+                          rt_ray *rays_device);
+/* Replaces rt_trace_radiance(RT_FB_F64X3) of n_pixels*samples rays followed by a reduction and a quantiser
+   of the caller's own (24 B per sample through memory and back).  Input: n_pixels * samples rays, pixel
+   p's samples at rays[p*samples .. p*samples + samples - 1].  c_s is exactly what rt_trace_radiance
+   computes for that ray: the once-normalised direction, depth, acceleration rule, culling switch and
+   arithmetic are the same.  Pixel p's value, S = samples:
+     weights == NULL, S == 1: c_0 itself, bit for bit -- the call equals rt_trace_radiance (trace_tile's
+                              one-sample rule; a -0.0 channel stays -0.0);
+     weights == NULL, S > 1:  acc = (0,0,0); acc = acc + c_s for s = 0..S-1 in that order; the value is
+                              acc * inv, inv = 1.0 / S formed once in fp64 on the host (for S = 4 the
+                              render's scale(acc, 0.25));
+     weights != NULL, S >= 1: acc = (0,0,0); acc = acc + c_s * w_s in order, the product rounded, then the
+                              sum rounded, no contraction and no final scale: the caller normalises the
+                              weights (HOST memory, S doubles, read during the call).
+   Record p is written in fb_format exactly as rt_trace_radiance writes a record: RT_FB_F64X3 / RT_FB_F32X3
+   convert as the render's store does; RT_FB_RGB8 goes through write_ppm's quantiser, a negative channel
+   stored as 0 and counted in negative_clamped, a NaN stored as 255 and not counted.  No row flip.
+   A zero, NaN or infinite ray is a traced miss whose colour comes from the NaN direction: it makes its
+   pixel NaN and touches no other pixel.
+   These are radiance launches: they use the context's radiance events, counters, reflection stack and
+   staging buffers, and rt_radiance_stats_get reports the most recent launch of either kind, with
+   rays = n_pixels*S and segments, hits, shadow_rays and unaccelerated counting every sample.  They change
+   nothing that rt_render_stats, rt_kernel_times, rt_get_info, rt_trace_stats or rt_path_stats_get report.
+   Errors: those of rt_trace_radiance (with n = n_pixels), and as RT_ERR_INVALID_ARG samples outside
+   1..RT_MAX_SAMPLES and n_pixels * samples > 2^31-1.  n_pixels == 0 is a no-op.
+   rays_device / out_device: device memory, 16-byte aligned; asynchronous on the context's stream. */
+int rt_trace_radiance_resolve_async(rt_ctx *ctx, const rt_ray *rays_device, size_t n_pixels, int samples,
+                                    const double *weights /* host, samples doubles; NULL = box */,
+                                    int depth, int fb_format, void *out_device);
+/* Synchronous; rays / out in host memory (staged through the radiance queries' grow-only buffers), or
+   (on_device = 1) device memory as above; stats may be NULL. */
+int rt_trace_radiance_resolve(rt_ctx *ctx, const rt_ray *rays, size_t n_pixels, int samples,
+                              const double *weights, int depth, int fb_format, void *out, int on_device,
+                              rt_radiance_stats *stats /* nullable */);
+/* Replaces rt_set_antialias(4) + rt_render for a pattern of the caller's: rt_camera_sample_rays followed by
+   rt_trace_radiance_resolve, in chunks of whole output rows.  Synchronous.  Writes the pixels of `rows`
+   (NULL = the full frame) in PPM row order in every format, record k*width + x, to host memory or
+   (out_on_device = 1) device memory, 16-byte aligned.  The context's grow-only ray buffer never exceeds
+   max_ray_bytes (one output row is the minimum); 0 means the default of 256 MiB.
+   Padding rows (a suffix of the output rows of an rt_rows) are not traced or counted; their records are
+   written as zero bytes.  So with the offsets (0,0) (.5,0) (0,.5) (.5,.5), box weights and RT_FB_RGB8,
+   every shard of an image is byte for byte rt_render's under rt_set_antialias(4).
+   stats: the counts summed over the call's chunk launches; kernel_ms the sum of the chunks' resolve-kernel
+   event times (ray generation is not in it).  rt_set_antialias does not apply to this call.
+   Errors: as rt_camera_sample_rays and rt_trace_radiance_resolve, except that the ray limit is tested
+   against width * samples (one output row, the smallest chunk), not rows->count * width * samples:
+   max_ray_bytes is what bounds the ray buffer. */
+int rt_render_samples(rt_ctx *ctx, const rt_camera *cam, int width, int height, int depth,
+                      const rt_rows *rows /* NULL = full frame */, const double *offsets_xy, int samples,
+                      const double *weights /* nullable */, int fb_format, void *out, int out_on_device,
+                      size_t max_ray_bytes /* 0 = default */, rt_radiance_stats *stats /* nullable */);
 
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
