@@ -1814,41 +1814,21 @@ struct BuildInfo {
   double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds
 };
 
-// The ray queries' own launch state (rt_trace_rays): nothing of it is shared
-// with the renders.  Created by the first query of a context.
-struct QueryState {
+// The launch state of one family of caller-ray queries.  rt_ctx keeps one per
+// family -- the ray queries (rt_trace_rays), the path queries (rt_trace_paths)
+// and the radiance queries (rt_trace_radiance, rt_trace_radiance_resolve,
+// rt_render_samples) -- and nothing of one is shared with another or with the
+// renders: each has its own counters, its own most recent launch and its own
+// staging.  Created by the family's first launch of a context (trace_state).
+struct TraceState {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool launched = false;
   DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
   PinnedBuf<unsigned long long> host;
-  DevBuf<rt_ray> rays;                 // rt_trace_rays from host memory: the batch on the device
-  DevBuf<rt_hit> hits;
-};
-
-// The path queries' launch state (rt_trace_paths), a sibling of QueryState:
-// shared with neither the renders nor the ray queries.  Created by the first
-// path query of a context.
-struct PathState {
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool launched = false;
-  DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
-  PinnedBuf<unsigned long long> host;
-  DevBuf<rt_ray> rays;                 // rt_trace_paths from host memory: the batch on the device
-  DevBuf<rt_vertex> verts;
-  DevBuf<rt_surface> surf;
-};
-
-// The radiance queries' launch state (rt_trace_radiance), a sibling of
-// PathState: shared with neither the renders nor the other queries.  Created
-// by the first radiance query of a context.
-struct RadianceState {
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool launched = false;
-  DevBuf<unsigned long long> ctr;      // [kShards][kShardStride], zeroed ahead of every launch
-  PinnedBuf<unsigned long long> host;
-  DevBuf<StackEnt> stack;              // grow-only: [depth - 1][grid * 64] of the largest launch seen
-  DevBuf<rt_ray> rays;                 // rt_trace_radiance from host memory: the batch on the device
-  DevBuf<uint8_t> out;
+  DevBuf<StackEnt> stack;              // radiance only, grow-only: [depth - 1][grid * 64] of the largest launch seen
+  // the synchronous calls from host memory: the batch on the device, and what it
+  // answers (hits; vertices and surfaces; colour records)
+  DevBuf<uint8_t> rays, out[2];
 };
 
 struct rt_ctx {
@@ -1869,9 +1849,7 @@ struct rt_ctx {
   LaunchTiming timing;
   OccCache occ;
   BuildInfo info;
-  QueryState query;
-  PathState paths;
-  RadianceState radiance;
+  TraceState query, paths, radiance;
   // grow-only scratch of the launches
   DevBuf<uint8_t> tmp;      // rt_render to host memory: the image on the device
   DevBuf<QRay> dq;          // kStackMerge: the deferred queue (and its slots' stacks)
@@ -3031,6 +3009,163 @@ int enqueue(rt_ctx *c, const LaunchReq &q) {
   return RT_OK;  // the counters are read back by rt_render_stats, after the stream drains
 }
 
+// ---- the caller-ray queries' host layer --------------------------------------
+// What the ray, path and radiance entry points below share: the checks, a
+// family's launch state, a launch's size, scene arguments and bracket, the
+// counter read, and the staging of the synchronous calls.
+
+// The checks, before any HIP call; an entry point lists them in the order it reports them.
+bool bad_batch(const rt_ctx *c, size_t n, size_t max_n, const void *in, const void *out) {
+  return !c || n > max_n || (n > 0 && (!in || !out));
+}
+int depth_status(int depth) {
+  return depth < 1 ? RT_ERR_INVALID_ARG : depth > RT_MAX_DEPTH ? RT_ERR_DEPTH : RT_OK;
+}
+bool misaligned(const void *a, const void *b, const void *d = nullptr) {  // device arrays: 16 bytes
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(d)) & 15u) != 0;
+}
+
+// A family's events, counters and pinned read-back buffer, once per context.
+int trace_state(rt_ctx *c, TraceState &q) {
+  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
+  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
+  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
+  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
+  if (!q.host.get()) {
+    RT_TRY(c, q.host.alloc(bytes));
+    std::memset(q.host.get(), 0, bytes);
+  }
+  return RT_OK;
+}
+
+// Dynamic LDS of the ordered walks' stacks: one wave per workgroup, [entry][lane]
+// at the base of dynamic LDS.  Deeper than kOrderedStack (12 KiB; bvh_args never
+// allows it) the launch takes the stackless walk and no LDS.
+size_t walk_lds(BvhArgs &bv) {
+  if (!bv.ordered) return 0;
+  const size_t lds = (size_t)bv.odepth * 64 * 8;
+  if (lds <= 12 * 1024) {
+    bv.ostk_off = 0;
+    return lds;
+  }
+  bv.ordered = bv.wide = 0;
+  return 0;
+}
+
+// One-wave workgroups for n lanes, grid-stride: at most 64 waves per CU.
+long long trace_grid(const rt_ctx *c, size_t n) {
+  return std::min<long long>(((long long)n + 63) / 64, (long long)c->n_cu * 64);
+}
+
+// The scene half of a launch's arguments (QueryArgs, PathArgs), counting into q.
+template <class A>
+void scene_args(const rt_ctx *c, const TraceState &q, A &a) {
+  const Scene &sc = c->scene;
+  a.geo = sc.geo.get(), a.rad = sc.rad.get(), a.n = sc.nsph;
+  a.accel = c->cull ? 1 : 0;
+  for (int k = 0; k < 3; k++) a.rlo[k] = sc.q_lo[k], a.rhi[k] = sc.q_hi[k];
+  a.bv = query_bvh_args(c);
+  a.counters = q.ctr.get();
+}
+void path_scene_args(const rt_ctx *c, const TraceState &q, PathArgs &a) {
+  scene_args(c, q, a);
+  a.mat = c->scene.mat.get(), a.lights = c->scene.lights.get(), a.nl = c->scene.nlight;
+}
+
+// The bracket of a launch on the context's stream: q's counters zeroed and its
+// events around `launch` (which enqueues the kernel), making it q's most recent.
+template <class Launch>
+int trace_launch(rt_ctx *c, TraceState &q, Launch launch) {
+  RT_TRY(c, hipMemsetAsync(q.ctr.get(), 0, q.ctr.bytes(), c->stream));
+  RT_TRY(c, hipEventRecord(q.ev0, c->stream));
+  launch();
+  RT_TRY(c, hipGetLastError());
+  RT_TRY(c, hipEventRecord(q.ev1, c->stream));
+  q.launched = true;
+  return RT_OK;
+}
+
+// The shared part of the stats getters: waits for the stream; q's most recent
+// launch as its counters summed over the shards and its event time, zeros
+// before the first.
+static_assert(kQueryCounters <= kRadianceCounters && kPathCounters <= kRadianceCounters, "sum[] holds every family's");
+struct TraceCounts {
+  unsigned long long sum[kRadianceCounters];
+  double ms;
+};
+int trace_counts(rt_ctx *c, TraceState &q, TraceCounts &t) {
+  t = TraceCounts{};
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));
+  if (!q.launched) return RT_OK;
+  float ms = 0.f;
+  RT_TRY(c, hipEventElapsedTime(&ms, q.ev0, q.ev1));
+  t.ms = ms;
+  unsigned long long *hc = q.host.get();
+  RT_TRY(c, hipMemcpy(hc, q.ctr.get(), q.host.bytes(), hipMemcpyDeviceToHost));
+  for (int sh = 0; sh < kShards; sh++)
+    for (int k = 0; k < kRadianceCounters; k++) t.sum[k] += hc[sh * kShardStride + k];
+  return RT_OK;
+}
+template <class S>  // rt_path_stats, and rt_radiance_stats' same fields
+void path_stats_of(const TraceCounts &t, S *st) {
+  st->rays = t.sum[kPcRays];
+  st->segments = t.sum[kPcSegments];
+  st->hits = t.sum[kPcHits];
+  st->shadow_rays = t.sum[kPcShadow];
+  st->tests_exact = t.sum[kPcExact];
+  st->tests_cull = t.sum[kPcCull];
+  st->unaccelerated = t.sum[kPcUnaccel];
+  st->kernel_ms = t.ms;
+}
+void radiance_stats_of(const TraceCounts &t, rt_radiance_stats *st) {
+  path_stats_of(t, st);
+  st->negative_clamped = t.sum[kRcNegative];
+}
+
+// One array of a synchronous call: the caller's, and where the launch finds it.
+enum { kStageIn = 1, kStageOut = 2 };
+struct Staged {
+  const void *p;         // the caller's pointer; nullptr: the array is not passed
+  DevBuf<uint8_t> *buf;  // its grow-only place on the device when p is host memory
+  size_t bytes;
+  int dir;               // kStageIn: copied to the device ahead of the launch; kStageOut: copied back after it
+  void *dev = nullptr;
+  template <class T>
+  T *as() const { return static_cast<T *>(dev); }
+};
+
+// The body of a synchronous entry point, after its checks: no rays is zero
+// stats; the arrays are used where they are (on_device) or staged around
+// `launch`, the family's _async form reading io[k].dev; then the family's stats.
+template <class Stats, size_t K, class Launch>
+int staged_call(rt_ctx *c, size_t n, Staged (&io)[K], bool on_device, int (*get)(rt_ctx *, Stats *), Stats *st,
+                Launch launch) {
+  if (n == 0) {
+    if (st) *st = Stats{};
+    return RT_OK;
+  }
+  RT_TRY(c, hipSetDevice(c->device));
+  int rc;
+  for (Staged &s : io) s.dev = const_cast<void *>(s.p);
+  if (!on_device) {
+    for (Staged &s : io) {
+      if (!s.p) continue;
+      if ((rc = grow(c, *s.buf, s.bytes)) != RT_OK) return rc;
+      s.dev = s.buf->get();
+    }
+    for (Staged &s : io)
+      if (s.p && (s.dir & kStageIn)) RT_TRY(c, hipMemcpyAsync(s.dev, s.p, s.bytes, hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = launch()) != RT_OK) return rc;
+  if (!on_device)
+    for (Staged &s : io)
+      if (s.p && (s.dir & kStageOut))
+        RT_TRY(c, hipMemcpyAsync(const_cast<void *>(s.p), s.dev, s.bytes, hipMemcpyDeviceToHost, c->stream));
+  Stats tmp;
+  return get(c, st ? st : &tmp);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3116,12 +3251,10 @@ void rt_destroy(rt_ctx *c) {
     if (c->timing.ev0[i]) (void)hipEventDestroy(c->timing.ev0[i]);
     if (c->timing.ev1[i]) (void)hipEventDestroy(c->timing.ev1[i]);
   }
-  if (c->query.ev0) (void)hipEventDestroy(c->query.ev0);
-  if (c->query.ev1) (void)hipEventDestroy(c->query.ev1);
-  if (c->paths.ev0) (void)hipEventDestroy(c->paths.ev0);
-  if (c->paths.ev1) (void)hipEventDestroy(c->paths.ev1);
-  if (c->radiance.ev0) (void)hipEventDestroy(c->radiance.ev0);
-  if (c->radiance.ev1) (void)hipEventDestroy(c->radiance.ev1);
+  for (TraceState *q : {&c->query, &c->paths, &c->radiance}) {
+    if (q->ev0) (void)hipEventDestroy(q->ev0);
+    if (q->ev1) (void)hipEventDestroy(q->ev1);
+  }
   if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;  // the buffers free themselves
@@ -3391,24 +3524,9 @@ int rt_render_tiles(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, co
 }
 
 // ---- ray queries (rt_query.h) ----------------------------------------------
-// The checks of the query entry points, before any HIP call.
 static int query_validate(const rt_ctx *c, int mode, const void *rays, size_t n, const void *hits) {
-  if (!c || (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_OCCLUDED) || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
-  if (n > 0 && (!rays || !hits)) return RT_ERR_INVALID_ARG;
-  return RT_OK;
-}
-
-// The query path's events, counters and pinned read-back buffer, once per context.
-static int query_state(rt_ctx *c) {
-  QueryState &q = c->query;
-  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
-  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
-  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
-  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
-  if (!q.host.get()) {
-    RT_TRY(c, q.host.alloc(bytes));
-    std::memset(q.host.get(), 0, bytes);
-  }
+  if (bad_batch(c, n, INT32_MAX, rays, hits)) return RT_ERR_INVALID_ARG;
+  if (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_OCCLUDED) return RT_ERR_INVALID_ARG;
   return RT_OK;
 }
 
@@ -3416,87 +3534,48 @@ int rt_trace_rays_async(rt_ctx *c, int mode, const rt_ray *rays, size_t n, rt_hi
   int rc = query_validate(c, mode, rays, n, hits);
   if (rc != RT_OK) return rc;
   if (n == 0) return RT_OK;
-  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u) return RT_ERR_INVALID_ARG;
+  if (misaligned(rays, hits)) return RT_ERR_INVALID_ARG;  // ahead of the scene, unlike the paths and the radiance
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   RT_TRY(c, hipSetDevice(c->device));
-  if ((rc = query_state(c)) != RT_OK) return rc;
-  const Scene &sc = c->scene;
+  if ((rc = trace_state(c, c->query)) != RT_OK) return rc;
   QueryArgs a{};
-  a.geo = sc.geo.get(), a.rad = sc.rad.get(), a.n = sc.nsph, a.nrays = (int)n;
-  a.accel = c->cull ? 1 : 0;
-  a.rays = rays, a.hits = hits;
-  for (int k = 0; k < 3; k++) a.rlo[k] = sc.q_lo[k], a.rhi[k] = sc.q_hi[k];
-  a.bv = query_bvh_args(c);
-  a.counters = c->query.ctr.get();
-  // the ordered walks' stacks: one wave per workgroup, [entry][lane] at the base of dynamic LDS
-  size_t lds = 0;
-  if (a.bv.ordered) {
-    lds = (size_t)a.bv.odepth * 64 * 8;
-    if (lds <= 12 * 1024) {
-      a.bv.ostk_off = 0;
-    } else {  // deeper than kOrderedStack (bvh_args never allows it): the stackless walk
-      a.bv.ordered = a.bv.wide = 0;
-      lds = 0;
-    }
-  }
-  const long long waves = ((long long)n + 63) / 64;
-  const int grid = (int)std::min<long long>(waves, (long long)c->n_cu * 64);
-  RT_TRY(c, hipMemsetAsync(c->query.ctr.get(), 0, c->query.ctr.bytes(), c->stream));
-  RT_TRY(c, hipEventRecord(c->query.ev0, c->stream));
-  if (mode == RT_QUERY_CLOSEST)
-    hipLaunchKernelGGL(query_kernel<RT_QUERY_CLOSEST>, dim3(grid), dim3(64), lds, c->stream, a);
-  else
-    hipLaunchKernelGGL(query_kernel<RT_QUERY_OCCLUDED>, dim3(grid), dim3(64), lds, c->stream, a);
-  RT_TRY(c, hipGetLastError());
-  RT_TRY(c, hipEventRecord(c->query.ev1, c->stream));
-  c->query.launched = true;
-  return RT_OK;
+  scene_args(c, c->query, a);
+  a.nrays = (int)n, a.rays = rays, a.hits = hits;
+  const size_t lds = walk_lds(a.bv);
+  const dim3 grid((unsigned)trace_grid(c, n));
+  return trace_launch(c, c->query, [&] {
+    if (mode == RT_QUERY_CLOSEST)
+      hipLaunchKernelGGL(query_kernel<RT_QUERY_CLOSEST>, grid, dim3(64), lds, c->stream, a);
+    else
+      hipLaunchKernelGGL(query_kernel<RT_QUERY_OCCLUDED>, grid, dim3(64), lds, c->stream, a);
+  });
 }
 
 int rt_trace_stats(rt_ctx *c, rt_query_stats *st) {
   if (!c || !st) return RT_ERR_INVALID_ARG;
   *st = rt_query_stats{};
-  RT_TRY(c, hipSetDevice(c->device));
-  RT_TRY(c, hipStreamSynchronize(c->stream));
-  if (!c->query.launched) return RT_OK;
-  float ms = 0.f;
-  RT_TRY(c, hipEventElapsedTime(&ms, c->query.ev0, c->query.ev1));
-  unsigned long long *hc = c->query.host.get();
-  RT_TRY(c, hipMemcpy(hc, c->query.ctr.get(), c->query.host.bytes(), hipMemcpyDeviceToHost));
-  unsigned long long sum[kQueryCounters] = {};
-  for (int sh = 0; sh < kShards; sh++)
-    for (int q = 0; q < kQueryCounters; q++) sum[q] += hc[sh * kShardStride + q];
-  st->rays = sum[kQcRays];
-  st->hits = sum[kQcHits];
-  st->tests_exact = sum[kQcExact];
-  st->tests_cull = sum[kQcCull];
-  st->rays_unaccelerated = sum[kQcUnaccel];
-  st->kernel_ms = ms;
+  TraceCounts t;
+  const int rc = trace_counts(c, c->query, t);
+  if (rc != RT_OK) return rc;
+  st->rays = t.sum[kQcRays];
+  st->hits = t.sum[kQcHits];
+  st->tests_exact = t.sum[kQcExact];
+  st->tests_cull = t.sum[kQcCull];
+  st->rays_unaccelerated = t.sum[kQcUnaccel];
+  st->kernel_ms = t.ms;
   return RT_OK;
 }
 
 int rt_trace_rays(rt_ctx *c, int mode, const rt_ray *rays, size_t n, rt_hit *hits, int on_device,
                   rt_query_stats *st) {
-  int rc = query_validate(c, mode, rays, n, hits);
+  const int rc = query_validate(c, mode, rays, n, hits);
   if (rc != RT_OK) return rc;
-  if (n == 0) {
-    if (st) *st = rt_query_stats{};
-    return RT_OK;
-  }
-  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  RT_TRY(c, hipSetDevice(c->device));
-  const rt_ray *d_rays = rays;
-  rt_hit *d_hits = hits;
-  if (!on_device) {
-    if ((rc = grow(c, c->query.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
-    if ((rc = grow(c, c->query.hits, n * sizeof(rt_hit))) != RT_OK) return rc;
-    d_rays = c->query.rays.get(), d_hits = c->query.hits.get();
-    RT_TRY(c, hipMemcpyAsync(c->query.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-  }
-  if ((rc = rt_trace_rays_async(c, mode, d_rays, n, d_hits)) != RT_OK) return rc;
-  if (!on_device) RT_TRY(c, hipMemcpyAsync(hits, d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
-  rt_query_stats tmp;
-  return rt_trace_stats(c, st ? st : &tmp);
+  if (n > 0 && !c->scene.has_scene) return RT_ERR_NO_SCENE;  // ahead of the _async form's alignment check
+  Staged io[] = {{rays, &c->query.rays, n * sizeof(rt_ray), kStageIn},
+                 {hits, &c->query.out[0], n * sizeof(rt_hit), kStageOut}};
+  return staged_call(c, n, io, on_device, rt_trace_stats, st, [&] {
+    return rt_trace_rays_async(c, mode, io[0].as<const rt_ray>(), n, io[1].as<rt_hit>());
+  });
 }
 
 int rt_camera_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows *rows, rt_ray *rays) {
@@ -3515,29 +3594,12 @@ int rt_camera_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows 
 }
 
 // ---- path queries (rt_paths.h) ---------------------------------------------
-// The checks of the path entry points, before any HIP call.
 static int path_validate(const rt_ctx *c, const void *rays, size_t n, int depth, const void *verts) {
-  if (!c || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
-  if (n > 0 && (!rays || !verts)) return RT_ERR_INVALID_ARG;
-  if (depth < 1) return RT_ERR_INVALID_ARG;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  if (bad_batch(c, n, INT32_MAX, rays, verts)) return RT_ERR_INVALID_ARG;
+  if (const int rc = depth_status(depth)) return rc;
   if (n == 0) return RT_OK;
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   if (c->scene.nlight > RT_PATH_MAX_LIGHTS) return RT_ERR_INVALID_ARG;
-  return RT_OK;
-}
-
-// The path queries' events, counters and pinned read-back buffer, once per context.
-static int path_state(rt_ctx *c) {
-  PathState &q = c->paths;
-  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
-  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
-  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
-  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
-  if (!q.host.get()) {
-    RT_TRY(c, q.host.alloc(bytes));
-    std::memset(q.host.get(), 0, bytes);
-  }
   return RT_OK;
 }
 
@@ -3545,98 +3607,44 @@ int rt_trace_paths_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, rt_
   int rc = path_validate(c, rays, n, depth, verts);
   if (rc != RT_OK) return rc;
   if (n == 0) return RT_OK;
-  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(verts) | reinterpret_cast<uintptr_t>(surf)) & 15u)
-    return RT_ERR_INVALID_ARG;
+  if (misaligned(rays, verts, surf)) return RT_ERR_INVALID_ARG;
   RT_TRY(c, hipSetDevice(c->device));
-  if ((rc = path_state(c)) != RT_OK) return rc;
-  const Scene &sc = c->scene;
+  if ((rc = trace_state(c, c->paths)) != RT_OK) return rc;
   PathArgs a{};
-  a.geo = sc.geo.get(), a.rad = sc.rad.get(), a.mat = sc.mat.get(), a.lights = sc.lights.get();
-  a.n = sc.nsph, a.nl = sc.nlight, a.nrays = (int)n, a.depth = depth;
-  a.accel = c->cull ? 1 : 0;
+  path_scene_args(c, c->paths, a);
+  a.nrays = (int)n, a.depth = depth;
   a.rays = rays, a.verts = verts, a.surf = surf;
-  for (int k = 0; k < 3; k++) a.rlo[k] = sc.q_lo[k], a.rhi[k] = sc.q_hi[k];
-  a.bv = query_bvh_args(c);
-  a.counters = c->paths.ctr.get();
-  // the ordered walks' stacks, sized as the query launch sizes them (rt_trace_rays_async)
-  size_t lds = 0;
-  if (a.bv.ordered) {
-    lds = (size_t)a.bv.odepth * 64 * 8;
-    if (lds <= 12 * 1024) {
-      a.bv.ostk_off = 0;
-    } else {
-      a.bv.ordered = a.bv.wide = 0;
-      lds = 0;
-    }
-  }
-  const long long waves = ((long long)n + 63) / 64;
-  const int grid = (int)std::min<long long>(waves, (long long)c->n_cu * 64);
-  RT_TRY(c, hipMemsetAsync(c->paths.ctr.get(), 0, c->paths.ctr.bytes(), c->stream));
-  RT_TRY(c, hipEventRecord(c->paths.ev0, c->stream));
-  if (surf)
-    hipLaunchKernelGGL(path_kernel<true>, dim3(grid), dim3(64), lds, c->stream, a);
-  else
-    hipLaunchKernelGGL(path_kernel<false>, dim3(grid), dim3(64), lds, c->stream, a);
-  RT_TRY(c, hipGetLastError());
-  RT_TRY(c, hipEventRecord(c->paths.ev1, c->stream));
-  c->paths.launched = true;
-  return RT_OK;
+  const size_t lds = walk_lds(a.bv);
+  const dim3 grid((unsigned)trace_grid(c, n));
+  return trace_launch(c, c->paths, [&] {
+    if (surf)
+      hipLaunchKernelGGL(path_kernel<true>, grid, dim3(64), lds, c->stream, a);
+    else
+      hipLaunchKernelGGL(path_kernel<false>, grid, dim3(64), lds, c->stream, a);
+  });
 }
 
 int rt_path_stats_get(rt_ctx *c, rt_path_stats *st) {
   if (!c || !st) return RT_ERR_INVALID_ARG;
   *st = rt_path_stats{};
-  RT_TRY(c, hipSetDevice(c->device));
-  RT_TRY(c, hipStreamSynchronize(c->stream));
-  if (!c->paths.launched) return RT_OK;
-  float ms = 0.f;
-  RT_TRY(c, hipEventElapsedTime(&ms, c->paths.ev0, c->paths.ev1));
-  unsigned long long *hc = c->paths.host.get();
-  RT_TRY(c, hipMemcpy(hc, c->paths.ctr.get(), c->paths.host.bytes(), hipMemcpyDeviceToHost));
-  unsigned long long sum[kPathCounters] = {};
-  for (int sh = 0; sh < kShards; sh++)
-    for (int q = 0; q < kPathCounters; q++) sum[q] += hc[sh * kShardStride + q];
-  st->rays = sum[kPcRays];
-  st->segments = sum[kPcSegments];
-  st->hits = sum[kPcHits];
-  st->shadow_rays = sum[kPcShadow];
-  st->tests_exact = sum[kPcExact];
-  st->tests_cull = sum[kPcCull];
-  st->unaccelerated = sum[kPcUnaccel];
-  st->kernel_ms = ms;
-  return RT_OK;
+  TraceCounts t;
+  const int rc = trace_counts(c, c->paths, t);
+  if (rc == RT_OK) path_stats_of(t, st);
+  return rc;
 }
 
 int rt_trace_paths(rt_ctx *c, const rt_ray *rays, size_t n, int depth, rt_vertex *verts, rt_surface *surf,
                    int on_device, rt_path_stats *st) {
-  int rc = path_validate(c, rays, n, depth, verts);
+  const int rc = path_validate(c, rays, n, depth, verts);
   if (rc != RT_OK) return rc;
-  if (n == 0) {
-    if (st) *st = rt_path_stats{};
-    return RT_OK;
-  }
-  RT_TRY(c, hipSetDevice(c->device));
-  PathState &q = c->paths;
   const size_t nrec = n * (size_t)depth;
-  const rt_ray *d_rays = rays;
-  rt_vertex *d_verts = verts;
-  rt_surface *d_surf = surf;
-  if (!on_device) {
-    if ((rc = grow(c, q.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
-    if ((rc = grow(c, q.verts, nrec * sizeof(rt_vertex))) != RT_OK) return rc;
-    if (surf && (rc = grow(c, q.surf, nrec * sizeof(rt_surface))) != RT_OK) return rc;
-    d_rays = q.rays.get(), d_verts = q.verts.get(), d_surf = surf ? q.surf.get() : nullptr;
-    RT_TRY(c, hipMemcpyAsync(q.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-    // surfaces of untraced levels are not touched: the caller's bytes travel there and back
-    if (surf) RT_TRY(c, hipMemcpyAsync(d_surf, surf, nrec * sizeof(rt_surface), hipMemcpyHostToDevice, c->stream));
-  }
-  if ((rc = rt_trace_paths_async(c, d_rays, n, depth, d_verts, d_surf)) != RT_OK) return rc;
-  if (!on_device) {
-    RT_TRY(c, hipMemcpyAsync(verts, d_verts, nrec * sizeof(rt_vertex), hipMemcpyDeviceToHost, c->stream));
-    if (surf) RT_TRY(c, hipMemcpyAsync(surf, d_surf, nrec * sizeof(rt_surface), hipMemcpyDeviceToHost, c->stream));
-  }
-  rt_path_stats tmp;
-  return rt_path_stats_get(c, st ? st : &tmp);
+  // surfaces of untraced levels are not touched: the caller's bytes travel there and back
+  Staged io[] = {{rays, &c->paths.rays, n * sizeof(rt_ray), kStageIn},
+                 {verts, &c->paths.out[0], nrec * sizeof(rt_vertex), kStageOut},
+                 {surf, &c->paths.out[1], nrec * sizeof(rt_surface), kStageIn | kStageOut}};
+  return staged_call(c, n, io, on_device, rt_path_stats_get, st, [&] {
+    return rt_trace_paths_async(c, io[0].as<const rt_ray>(), n, depth, io[1].as<rt_vertex>(), io[2].as<rt_surface>());
+  });
 }
 
 // ---- radiance queries (rt_radiance.h) --------------------------------------
@@ -3645,28 +3653,15 @@ static size_t radiance_record(int fmt) {
   return fmt == RT_FB_RGB8 ? 3 : fmt == RT_FB_F32X3 ? 3 * sizeof(float) : fmt == RT_FB_F64X3 ? 3 * sizeof(double) : 0;
 }
 
-// The checks of the radiance entry points, before any HIP call.
-static int radiance_validate(const rt_ctx *c, const void *rays, size_t n, int depth, int fmt, const void *out) {
-  if (!c || n > (size_t)INT32_MAX) return RT_ERR_INVALID_ARG;
-  if (n > 0 && (!rays || !out)) return RT_ERR_INVALID_ARG;
-  if (depth < 1 || radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+// n records of `samples` rays each: 1 for rt_trace_radiance.
+static int radiance_validate(const rt_ctx *c, const void *rays, size_t n, int samples, int depth, int fmt,
+                             const void *out) {
+  if (samples < 1 || samples > RT_MAX_SAMPLES) return RT_ERR_INVALID_ARG;
+  if (bad_batch(c, n, (size_t)INT32_MAX / (size_t)samples, rays, out)) return RT_ERR_INVALID_ARG;
+  if (radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
+  if (const int rc = depth_status(depth)) return rc;
   if (n == 0) return RT_OK;
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  return RT_OK;
-}
-
-// The radiance queries' events, counters and pinned read-back buffer, once per context.
-static int radiance_state(rt_ctx *c) {
-  RadianceState &q = c->radiance;
-  if (!q.ev0) RT_TRY(c, hipEventCreate(&q.ev0));
-  if (!q.ev1) RT_TRY(c, hipEventCreate(&q.ev1));
-  const size_t bytes = kShards * kShardStride * sizeof(unsigned long long);
-  if (!q.ctr.get()) RT_TRY(c, q.ctr.alloc(bytes));
-  if (!q.host.get()) {
-    RT_TRY(c, q.host.alloc(bytes));
-    std::memset(q.host.get(), 0, bytes);
-  }
   return RT_OK;
 }
 
@@ -3690,35 +3685,17 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
                            const ResolveSpec *rv) {
   int rc;
   RT_TRY(c, hipSetDevice(c->device));
-  if ((rc = radiance_state(c)) != RT_OK) return rc;
-  const Scene &sc = c->scene;
-  RadianceState &rs = c->radiance;
+  TraceState &rs = c->radiance;
+  if ((rc = trace_state(c, rs)) != RT_OK) return rc;
   RadianceArgs a{};
-  PathArgs &p = a.q;
-  p.geo = sc.geo.get(), p.rad = sc.rad.get(), p.mat = sc.mat.get(), p.lights = sc.lights.get();
-  p.n = sc.nsph, p.nl = sc.nlight, p.nrays = (int)n, p.depth = depth;
-  p.accel = c->cull ? 1 : 0;
-  p.rays = rays;
-  for (int k = 0; k < 3; k++) p.rlo[k] = sc.q_lo[k], p.rhi[k] = sc.q_hi[k];
-  p.bv = query_bvh_args(c);
-  p.counters = rs.ctr.get();
-  a.amb = D3{sc.amb[0], sc.amb[1], sc.amb[2]};
+  path_scene_args(c, rs, a.q);
+  a.q.nrays = (int)n, a.q.depth = depth, a.q.rays = rays;
+  a.amb = D3{c->scene.amb[0], c->scene.amb[1], c->scene.amb[2]};
   a.fmt = fmt, a.out = out;
-  // the ordered walks' stacks, sized as the path launch sizes them (rt_trace_paths_async)
-  size_t lds = 0;
-  if (p.bv.ordered) {
-    lds = (size_t)p.bv.odepth * 64 * 8;
-    if (lds <= 12 * 1024) {
-      p.bv.ostk_off = 0;
-    } else {
-      p.bv.ordered = p.bv.wide = 0;
-      lds = 0;
-    }
-  }
-  a.park_off = (int)lds;  // the wave's parked colours behind them
+  size_t lds = walk_lds(a.q.bv);
+  a.park_off = (int)lds;  // the wave's parked colours behind the walks' stacks
   lds += 64 * sizeof(D3);
-  const long long waves = ((long long)n + 63) / 64;
-  long long grid = std::min<long long>(waves, (long long)c->n_cu * 64);
+  long long grid = trace_grid(c, n);
   // the reflection stack belongs to the launch's lane slots, so the grid bounds it, not n; depth 1
   // spawns nothing and takes none
   if (depth > 1) {
@@ -3728,11 +3705,11 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
     a.stack = rs.stack.get();
   }
   a.sstride = (unsigned)grid * 64u;
-  RT_TRY(c, hipMemsetAsync(rs.ctr.get(), 0, rs.ctr.bytes(), c->stream));
-  RT_TRY(c, hipEventRecord(rs.ev0, c->stream));
-  if (!rv) {
-    hipLaunchKernelGGL(radiance_kernel<false>, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
-  } else {
+  return trace_launch(c, rs, [&] {
+    if (!rv) {
+      hipLaunchKernelGGL(radiance_kernel<false>, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
+      return;
+    }
     ResolveArgs ra{};
     ra.r = a;
     ra.samples = rv->samples;
@@ -3741,70 +3718,35 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
     ra.inv = 1.0 / (double)rv->samples;
     for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
     hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
-  }
-  RT_TRY(c, hipGetLastError());
-  RT_TRY(c, hipEventRecord(rs.ev1, c->stream));
-  rs.launched = true;
-  return RT_OK;
+  });
 }
 
 int rt_trace_radiance_async(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out) {
-  int rc = radiance_validate(c, rays, n, depth, fmt, out);
+  const int rc = radiance_validate(c, rays, n, 1, depth, fmt, out);
   if (rc != RT_OK) return rc;
   if (n == 0) return RT_OK;
-  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+  if (misaligned(rays, out)) return RT_ERR_INVALID_ARG;
   return radiance_launch(c, rays, n, depth, fmt, out, nullptr);
 }
 
 int rt_radiance_stats_get(rt_ctx *c, rt_radiance_stats *st) {
   if (!c || !st) return RT_ERR_INVALID_ARG;
   *st = rt_radiance_stats{};
-  RT_TRY(c, hipSetDevice(c->device));
-  RT_TRY(c, hipStreamSynchronize(c->stream));
-  RadianceState &rs = c->radiance;
-  if (!rs.launched) return RT_OK;
-  float ms = 0.f;
-  RT_TRY(c, hipEventElapsedTime(&ms, rs.ev0, rs.ev1));
-  unsigned long long *hc = rs.host.get();
-  RT_TRY(c, hipMemcpy(hc, rs.ctr.get(), rs.host.bytes(), hipMemcpyDeviceToHost));
-  unsigned long long sum[kRadianceCounters] = {};
-  for (int sh = 0; sh < kShards; sh++)
-    for (int q = 0; q < kRadianceCounters; q++) sum[q] += hc[sh * kShardStride + q];
-  st->rays = sum[kPcRays];
-  st->segments = sum[kPcSegments];
-  st->hits = sum[kPcHits];
-  st->shadow_rays = sum[kPcShadow];
-  st->tests_exact = sum[kPcExact];
-  st->tests_cull = sum[kPcCull];
-  st->unaccelerated = sum[kPcUnaccel];
-  st->negative_clamped = sum[kRcNegative];
-  st->kernel_ms = ms;
-  return RT_OK;
+  TraceCounts t;
+  const int rc = trace_counts(c, c->radiance, t);
+  if (rc == RT_OK) radiance_stats_of(t, st);
+  return rc;
 }
 
 int rt_trace_radiance(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out, int on_device,
                       rt_radiance_stats *st) {
-  int rc = radiance_validate(c, rays, n, depth, fmt, out);
+  const int rc = radiance_validate(c, rays, n, 1, depth, fmt, out);
   if (rc != RT_OK) return rc;
-  if (n == 0) {
-    if (st) *st = rt_radiance_stats{};
-    return RT_OK;
-  }
-  RT_TRY(c, hipSetDevice(c->device));
-  RadianceState &rs = c->radiance;
-  const size_t out_bytes = n * radiance_record(fmt);
-  const rt_ray *d_rays = rays;
-  void *d_out = out;
-  if (!on_device) {
-    if ((rc = grow(c, rs.rays, n * sizeof(rt_ray))) != RT_OK) return rc;
-    if ((rc = grow(c, rs.out, out_bytes)) != RT_OK) return rc;
-    d_rays = rs.rays.get(), d_out = rs.out.get();
-    RT_TRY(c, hipMemcpyAsync(rs.rays.get(), rays, n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-  }
-  if ((rc = rt_trace_radiance_async(c, d_rays, n, depth, fmt, d_out)) != RT_OK) return rc;
-  if (!on_device) RT_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  rt_radiance_stats tmp;
-  return rt_radiance_stats_get(c, st ? st : &tmp);
+  Staged io[] = {{rays, &c->radiance.rays, n * sizeof(rt_ray), kStageIn},
+                 {out, &c->radiance.out[0], n * radiance_record(fmt), kStageOut}};
+  return staged_call(c, n, io, on_device, rt_radiance_stats_get, st, [&] {
+    return rt_trace_radiance_async(c, io[0].as<const rt_ray>(), n, depth, fmt, io[1].dev);
+  });
 }
 
 // ---- multi-sample pixels (rt_radiance.h, kResolve) --------------------------
@@ -3843,47 +3785,25 @@ int rt_camera_sample_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const r
   return sample_rays_launch(c, cam, W, H, r, 0, r.count, offsets, samples, rays);
 }
 
-// The checks of the resolving entry points, before any HIP call: rt_trace_radiance's, and the sample count.
-static int resolve_validate(const rt_ctx *c, const void *rays, size_t n, int samples, int depth, int fmt,
-                            const void *out) {
-  if (!c || samples < 1 || samples > RT_MAX_SAMPLES) return RT_ERR_INVALID_ARG;
-  if (n > (size_t)INT32_MAX / (size_t)samples) return RT_ERR_INVALID_ARG;
-  return radiance_validate(c, rays, n, depth, fmt, out);
-}
-
 int rt_trace_radiance_resolve_async(rt_ctx *c, const rt_ray *rays, size_t n, int samples, const double *weights,
                                     int depth, int fmt, void *out) {
-  int rc = resolve_validate(c, rays, n, samples, depth, fmt, out);
+  const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
   if (n == 0) return RT_OK;
-  if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u) return RT_ERR_INVALID_ARG;
+  if (misaligned(rays, out)) return RT_ERR_INVALID_ARG;
   const ResolveSpec rv{samples, weights};
   return radiance_launch(c, rays, n, depth, fmt, out, &rv);
 }
 
 int rt_trace_radiance_resolve(rt_ctx *c, const rt_ray *rays, size_t n, int samples, const double *weights, int depth,
                               int fmt, void *out, int on_device, rt_radiance_stats *st) {
-  int rc = resolve_validate(c, rays, n, samples, depth, fmt, out);
+  const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
-  if (n == 0) {
-    if (st) *st = rt_radiance_stats{};
-    return RT_OK;
-  }
-  RT_TRY(c, hipSetDevice(c->device));
-  RadianceState &rs = c->radiance;
-  const size_t nrays = n * (size_t)samples, out_bytes = n * radiance_record(fmt);
-  const rt_ray *d_rays = rays;
-  void *d_out = out;
-  if (!on_device) {
-    if ((rc = grow(c, rs.rays, nrays * sizeof(rt_ray))) != RT_OK) return rc;
-    if ((rc = grow(c, rs.out, out_bytes)) != RT_OK) return rc;
-    d_rays = rs.rays.get(), d_out = rs.out.get();
-    RT_TRY(c, hipMemcpyAsync(rs.rays.get(), rays, nrays * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-  }
-  if ((rc = rt_trace_radiance_resolve_async(c, d_rays, n, samples, weights, depth, fmt, d_out)) != RT_OK) return rc;
-  if (!on_device) RT_TRY(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  rt_radiance_stats tmp;
-  return rt_radiance_stats_get(c, st ? st : &tmp);
+  Staged io[] = {{rays, &c->radiance.rays, n * (size_t)samples * sizeof(rt_ray), kStageIn},
+                 {out, &c->radiance.out[0], n * radiance_record(fmt), kStageOut}};
+  return staged_call(c, n, io, on_device, rt_radiance_stats_get, st, [&] {
+    return rt_trace_radiance_resolve_async(c, io[0].as<const rt_ray>(), n, samples, weights, depth, fmt, io[1].dev);
+  });
 }
 
 // The ray buffer of rt_render_samples when the caller names no bound: a choice, 4 Mi rays
@@ -3899,8 +3819,8 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   const long long row_rays = (long long)W * samples;  // one output row: the smallest chunk
   if (row_rays > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
   const size_t rec = radiance_record(fmt);
-  if (depth < 1 || rec == 0) return RT_ERR_INVALID_ARG;
-  if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
+  if (rec == 0) return RT_ERR_INVALID_ARG;
+  if ((rc = depth_status(depth)) != RT_OK) return rc;
   if (r.count == 0) {
     if (st) *st = rt_radiance_stats{};
     return RT_OK;
@@ -3921,25 +3841,25 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   const size_t cap = max_ray_bytes ? max_ray_bytes : kSampleRayBytes;
   long long chunk = std::max<long long>(1, (long long)(cap / ((size_t)row_rays * sizeof(rt_ray))));
   chunk = std::min<long long>(chunk, (long long)INT32_MAX / row_rays);
-  RadianceState &rs = c->radiance;
+  TraceState &rs = c->radiance;  // the chunks' rays and, for host memory, their records: the family's staging
   uint8_t *dst = static_cast<uint8_t *>(out);
   const ResolveSpec rv{samples, weights};
-  rt_radiance_stats sum{}, one{};
+  TraceCounts sum{}, one;
   for (int k0 = 0; k0 < real; k0 += (int)chunk) {
     const int nr = (int)std::min<long long>(chunk, real - k0);
     const size_t npx = (size_t)nr * W, off = (size_t)k0 * W * rec;
     if ((rc = grow(c, rs.rays, npx * samples * sizeof(rt_ray))) != RT_OK) return rc;
-    if (!on_device && (rc = grow(c, rs.out, npx * rec)) != RT_OK) return rc;
-    if ((rc = sample_rays_launch(c, cam, W, H, r, k0, nr, offsets, samples, rs.rays.get())) != RT_OK) return rc;
+    if (!on_device && (rc = grow(c, rs.out[0], npx * rec)) != RT_OK) return rc;
+    rt_ray *rays = reinterpret_cast<rt_ray *>(rs.rays.get());
+    if ((rc = sample_rays_launch(c, cam, W, H, r, k0, nr, offsets, samples, rays)) != RT_OK) return rc;
     // a chunk's records begin where the previous chunk's end: aligned as the format, not to 16 bytes (the
     // kernel's packed RGB8 store tests the alignment it needs)
-    void *d_out = on_device ? static_cast<void *>(dst + off) : static_cast<void *>(rs.out.get());
-    if ((rc = radiance_launch(c, rs.rays.get(), npx, depth, fmt, d_out, &rv)) != RT_OK) return rc;
+    void *d_out = on_device ? static_cast<void *>(dst + off) : static_cast<void *>(rs.out[0].get());
+    if ((rc = radiance_launch(c, rays, npx, depth, fmt, d_out, &rv)) != RT_OK) return rc;
     if (!on_device) RT_TRY(c, hipMemcpyAsync(dst + off, d_out, npx * rec, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = rt_radiance_stats_get(c, &one)) != RT_OK) return rc;
-    sum.rays += one.rays, sum.segments += one.segments, sum.hits += one.hits, sum.shadow_rays += one.shadow_rays;
-    sum.tests_exact += one.tests_exact, sum.tests_cull += one.tests_cull, sum.unaccelerated += one.unaccelerated;
-    sum.negative_clamped += one.negative_clamped, sum.kernel_ms += one.kernel_ms;
+    if ((rc = trace_counts(c, rs, one)) != RT_OK) return rc;
+    for (int k = 0; k < kRadianceCounters; k++) sum.sum[k] += one.sum[k];
+    sum.ms += one.ms;
   }
   // padding rows: not traced, not counted, zero bytes
   const size_t pad_off = (size_t)real * W * rec, pad = (size_t)(r.count - real) * W * rec;
@@ -3951,7 +3871,10 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
       std::memset(dst + pad_off, 0, pad);
     }
   }
-  if (st) *st = sum;
+  if (st) {
+    *st = rt_radiance_stats{};
+    radiance_stats_of(sum, st);
+  }
   return RT_OK;
 }
 

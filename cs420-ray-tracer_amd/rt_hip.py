@@ -507,15 +507,8 @@ class Renderer:
         the launch's rt_query_stats."""
         import numpy as np
 
-        o = np.asarray(origins, np.float64).reshape(-1, 3)
-        d = np.asarray(directions, np.float64).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"{n} origins, {d.shape[0]} directions")
-        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax, reserved
-        rays[:, 0:3] = o
-        rays[:, 3:6] = d
-        rays[:, 6] = np.inf if tmax is None else np.broadcast_to(np.asarray(tmax, np.float64), (n,))
+        rays = _pack_rays(origins, directions, np.inf if tmax is None else tmax)
+        n = rays.shape[0]
         hits = np.zeros(n, np.dtype([("t", np.float64), ("sphere", np.int32), ("occluded", np.int32)]))
         st = rt_query_stats()
         _check(self._L.rt_trace_rays(self._ctx, mode, C.c_void_p(rays.ctypes.data), n, C.c_void_p(hits.ctypes.data), 0,
@@ -549,14 +542,8 @@ class Renderer:
         levels are zeros) and the launch's rt_path_stats."""
         import numpy as np
 
-        o = np.asarray(origins, np.float64).reshape(-1, 3)
-        d = np.asarray(directions, np.float64).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"{n} origins, {d.shape[0]} directions")
-        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
-        rays[:, 0:3] = o
-        rays[:, 3:6] = d
+        rays = _pack_rays(origins, directions)
+        n = rays.shape[0]
         verts = np.zeros((max(depth, 0), n), _path_dtype("VERTEX_DTYPE"))
         surf = np.zeros((max(depth, 0), n), _path_dtype("SURFACE_DTYPE")) if surfaces else None
         st = rt_path_stats()
@@ -586,16 +573,9 @@ class Renderer:
         RT_FB_RGB8), ray i in row i, and the launch's rt_radiance_stats."""
         import numpy as np
 
-        o = np.asarray(origins, np.float64).reshape(-1, 3)
-        d = np.asarray(directions, np.float64).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"{n} origins, {d.shape[0]} directions")
-        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
-        rays[:, 0:3] = o
-        rays[:, 3:6] = d
-        dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.float64)
-        out = np.zeros((n, 3), dtype)
+        rays = _pack_rays(origins, directions)
+        n = rays.shape[0]
+        out = np.zeros((n, 3), _fb_dtype(fmt, np.float64))
         st = rt_radiance_stats()
         _check(self._L.rt_trace_radiance(self._ctx, C.c_void_p(rays.ctypes.data), n, depth, fmt,
                                          C.c_void_p(out.ctypes.data), 0, C.byref(st)),
@@ -633,19 +613,12 @@ class Renderer:
         the format's dtype and the launch's rt_radiance_stats."""
         import numpy as np
 
-        o = np.asarray(origins, np.float64).reshape(-1, 3)
-        d = np.asarray(directions, np.float64).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"{n} origins, {d.shape[0]} directions")
+        rays = _pack_rays(origins, directions)
+        n = rays.shape[0]
         if samples >= 1 and n % samples:
             raise ValueError(f"{n} rays are not a multiple of {samples} samples")
         npix = n // samples if samples >= 1 else n
-        rays = np.zeros((n, 8), np.float64)  # rt_ray: origin, direction, tmax and reserved (ignored)
-        rays[:, 0:3] = o
-        rays[:, 3:6] = d
-        dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.float64)
-        out = np.zeros((npix, 3), dtype)
+        out = np.zeros((npix, 3), _fb_dtype(fmt, np.float64))
         w = _sample_weights(weights, samples)
         st = rt_radiance_stats()
         _check(self._L.rt_trace_radiance_resolve(self._ctx, C.c_void_p(rays.ctypes.data), npix, samples, w, depth,
@@ -677,8 +650,7 @@ class Renderer:
         if out is None:
             import numpy as np
 
-            dtype = {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, np.uint8)
-            out = np.zeros((max(count, 0) * width, 3), dtype)
+            out = np.zeros((max(count, 0) * width, 3), _fb_dtype(fmt, np.uint8))
         ptr = out if isinstance(out, int) else _addr(out)
         st = rt_radiance_stats()
         _check(self._L.rt_render_samples(self._ctx, C.byref(cam), width, height, depth,
@@ -819,6 +791,31 @@ def _sample_weights(weights, samples: int):
     if n != samples:
         raise ValueError(f"{n} weights for {samples} samples")
     return w
+
+
+def _pack_rays(origins, directions, tmax=None):
+    """The [n, 8] float64 rt_ray records (origin, direction, tmax, reserved) of Ray(origins[i],
+    directions[i]); tmax a scalar or [n], None = 0 (the calls that ignore it)."""
+    import numpy as np
+
+    o = np.asarray(origins, np.float64).reshape(-1, 3)
+    d = np.asarray(directions, np.float64).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError(f"{n} origins, {d.shape[0]} directions")
+    rays = np.zeros((n, 8), np.float64)
+    rays[:, 0:3] = o
+    rays[:, 3:6] = d
+    if tmax is not None:
+        rays[:, 6] = np.broadcast_to(np.asarray(tmax, np.float64), (n,))
+    return rays
+
+
+def _fb_dtype(fmt: int, default):
+    """The numpy dtype of a record format's channels; `default` for an unknown one (the call rejects it)."""
+    import numpy as np
+
+    return {RT_FB_RGB8: np.uint8, RT_FB_F32X3: np.float32, RT_FB_F64X3: np.float64}.get(fmt, default)
 
 
 def _addr(buf) -> int:
