@@ -27,6 +27,9 @@
 // --supersample N (1..8, one device only: not with --gpus, --devices or -a):
 // N x N samples per pixel at the offsets (a/N, b/N), box-filtered, through
 // rt_render_samples; --supersample 2 writes the bytes of -a.
+// --sample-devices LIST (only with --supersample; not with --gpus, --devices or
+// -a): the supersampled frame as row shards, one per listed device, through the
+// device group (rt_group_render_samples); the same lines, file and --json fields.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -58,19 +61,22 @@ struct Opts {
   std::vector<int> devices;  // --devices LIST: the pass renders through rt_group_*
   int frames = -1, batch = -1;  // --frames N [--batch B]: a sequence per pass (rt_group_render_frames); -1: not given
   int supersample = 0;  // --supersample N: N x N samples per pixel through rt_render_samples; 0: not given
+  std::vector<int> sample_devices;  // --sample-devices LIST: --supersample through rt_group_render_samples
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a | --supersample N] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
                "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
-               "          [--json] [scene.txt]\n"
+               "          [--sample-devices D0,D1,...] [--json] [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
                "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
                "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
                "                  sequence and writes the last; --batch B (0..%d, 0 = %d): frames per launch\n"
                "  --supersample N N x N box-filtered samples per pixel (1..8); one device: not with --gpus,\n"
-               "                  --devices or -a\n",
+               "                  --devices or -a\n"
+               "  --sample-devices LIST  with --supersample: the frame's row shards, one per listed device,\n"
+               "                  through the device group; not with --gpus, --devices or -a\n",
                argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
   return 2;
 }
@@ -129,7 +135,8 @@ int render_single(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8
   return 0;
 }
 
-// --supersample N: the full frame through rt_render_samples, N x N samples per pixel at (a/N, b/N), a fastest.
+// --supersample N: the full frame through rt_render_samples, N x N samples per pixel at (a/N, b/N), a fastest;
+// with --sample-devices through rt_group_render_samples on a group of band 8.
 int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
   const int N = o.supersample;
   std::vector<double> offsets;
@@ -138,10 +145,34 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
       offsets.push_back((double)a / N);
       offsets.push_back((double)b / N);
     }
+  rt_radiance_stats st{};
+  auto report = [&] {
+    res.kernel_ms = st.kernel_ms;
+    res.primary = st.rays;
+    res.shadow = st.shadow_rays;
+    res.reflect = st.segments - st.rays;
+    res.negative = st.negative_clamped;
+  };
+  if (!o.sample_devices.empty()) {
+    rt_group *grp = nullptr;
+    CK(rt_group_create(o.sample_devices.data(), (int)o.sample_devices.size(), 8, &grp));
+    int rc = rt_group_upload_scene(grp, &sc);
+    for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
+      auto t0 = std::chrono::high_resolution_clock::now();
+      rc = rt_group_render_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), N * N, nullptr, RT_FB_RGB8,
+                                   img, 0, &st);
+      auto t1 = std::chrono::high_resolution_clock::now();
+      res.wall_s = std::chrono::duration<double>(t1 - t0).count();
+    }
+    if (rc != RT_OK)
+      std::fprintf(stderr, "device group failed: %s (%s)\n", rt_error_string(rc), rt_group_last_error(grp));
+    rt_group_destroy(grp);
+    report();
+    return rc != RT_OK ? 1 : 0;
+  }
   rt_ctx *ctx = nullptr;
   CK(rt_create(o.device, &ctx));
   CK(rt_upload_scene(ctx, &sc));
-  rt_radiance_stats st{};
   for (int it = 0; it < o.repeat; it++) {
     auto t0 = std::chrono::high_resolution_clock::now();
     CK(rt_render_samples(ctx, &cam, o.width, o.height, o.depth, nullptr, offsets.data(), N * N, nullptr, RT_FB_RGB8,
@@ -149,11 +180,7 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
     auto t1 = std::chrono::high_resolution_clock::now();
     res.wall_s = std::chrono::duration<double>(t1 - t0).count();
   }
-  res.kernel_ms = st.kernel_ms;
-  res.primary = st.rays;
-  res.shadow = st.shadow_rays;
-  res.reflect = st.segments - st.rays;
-  res.negative = st.negative_clamped;
+  report();
   rt_destroy(ctx);
   return 0;
 }
@@ -334,7 +361,8 @@ int render_pass(const Opts &o, const rt_scene &sc, const rt_camera &cam, const c
         "{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"depth\": %d, \"gpus\": %d, %s\"rays\": %llu, "
         "\"primary\": %llu, \"shadow\": %llu, \"reflect\": %llu, \"kernel_ms\": %.4f, \"wall_ms\": %.4f, "
         "\"mrays_per_s\": %.2f}\n",
-        o.scene.c_str(), o.width, o.height, o.depth, o.devices.empty() ? o.gpus : (int)o.devices.size(),
+        o.scene.c_str(), o.width, o.height, o.depth,
+        !o.sample_devices.empty() ? (int)o.sample_devices.size() : o.devices.empty() ? o.gpus : (int)o.devices.size(),
         frames.c_str(), (unsigned long long)rays,
         (unsigned long long)res.primary, (unsigned long long)res.shadow, (unsigned long long)res.reflect,
         res.kernel_ms, res.wall_s * 1e3, rays / (res.kernel_ms * 1e-3) / 1e6);
@@ -380,6 +408,7 @@ int main(int argc, char **argv) {
     else if (a == "--force-gather") o.force_gather = true;
     else if (a == "-a") o.samples = 4;
     else if (a == "--supersample") { if (!next(o.supersample) || o.supersample < 1 || o.supersample > 8) return usage(argv[0]); }
+    else if (a == "--sample-devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.sample_devices)) return usage(argv[0]); }
     else if (a == "--json") o.json = true;
     else if (a == "-h" || a == "--help") return usage(argv[0]);
     else o.scene = a;  // any other argument is the scene path, as main.cpp:103-110
@@ -387,6 +416,7 @@ int main(int argc, char **argv) {
   if (o.width <= 0 || o.height <= 0 || o.gpus < 1 || o.repeat < 1) return usage(argv[0]);
   if (!o.devices.empty() && (o.gpus > 1 || o.force_gather)) return usage(argv[0]);
   if (o.supersample && (gpus_given || !o.devices.empty() || o.force_gather || o.samples != 1)) return usage(argv[0]);
+  if (!o.sample_devices.empty() && !o.supersample) return usage(argv[0]);  // with --supersample: the line above
   if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116

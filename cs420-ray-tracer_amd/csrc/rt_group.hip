@@ -44,8 +44,10 @@
 //       of batch b-2's iteration -- so no wait can be skipped, and with more
 //       streams than hardware queues no barrier sits in front of the packet
 //       it waits for.
-//   (e) rt_group_render and rt_group_render_frames share the buffers and the
-//       events (one frame uses slot 0): both calls are synchronous and return
+//   (e) rt_group_render, rt_group_render_samples (rt_group_render's flow with
+//       rt_render_samples_async per shard, records of 3, 12 or 24 bytes and
+//       place_rows_kernel) and rt_group_render_frames share the buffers and the
+//       events (one frame uses slot 0): all are synchronous and return
 //       with every stream of the group idle -- each member's last work is its
 //       done event, which the assembly stream waits for before the host waits
 //       for the assembly stream; a failed call drains every stream -- so
@@ -119,6 +121,31 @@ __global__ __launch_bounds__(kPlaceBlock) void place_frames_kernel(const uint8_t
   const uint8_t *s = src + ((size_t)f * (size_t)R + (size_t)k) * (size_t)W * 3;
   uint8_t *d = dst + (size_t)f * dst_stride + (size_t)y * (size_t)W * 3;
   copy_row(s, d, W * 3);
+}
+
+// place_shard_kernel for rows of `row_bytes` bytes (rt_group_render_samples: W records of 3, 12 or 24
+// bytes, which may pass 2^31 together): the same row mapping and the same choice of copy width per row.
+__global__ __launch_bounds__(kPlaceBlock) void place_rows_kernel(const uint8_t *__restrict__ src,
+                                                                 uint8_t *__restrict__ dst, size_t row_bytes, int H,
+                                                                 int band, int G, int r, int R) {
+  const int k = blockIdx.x;
+  if (k >= R) return;
+  const long long y = (long long)(k / band) * band * G + (long long)r * band + (k % band);
+  if (y >= H) return;
+  const uint8_t *__restrict__ s = src + (size_t)k * row_bytes;
+  uint8_t *__restrict__ d = dst + (size_t)y * row_bytes;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) | (uintptr_t)row_bytes;
+  if ((bits & 15) == 0) {
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(s);
+    uint4 *d4 = reinterpret_cast<uint4 *>(d);
+    for (size_t i = threadIdx.x; i < row_bytes / 16; i += kPlaceBlock) d4[i] = s4[i];
+  } else if ((bits & 3) == 0) {
+    const unsigned *s1 = reinterpret_cast<const unsigned *>(s);
+    unsigned *d1 = reinterpret_cast<unsigned *>(d);
+    for (size_t i = threadIdx.x; i < row_bytes / 4; i += kPlaceBlock) d1[i] = s1[i];
+  } else {
+    for (size_t i = threadIdx.x; i < row_bytes; i += kPlaceBlock) d[i] = s[i];
+  }
 }
 
 // Grow-only device memory on one device.
@@ -279,6 +306,69 @@ int render(rt_group *g, const rt_camera *cam, int W, int H, int depth, uint8_t *
     sum.negative_clamped += st.negative_clamped;
     sum.tests_exact += st.tests_exact;
     sum.tests_cull += st.tests_cull;
+    sum.kernel_ms = std::max(sum.kernel_ms, st.kernel_ms);
+  }
+  if (stats) *stats = sum;
+  return RT_OK;
+}
+
+// render()'s flow for a multi-sample frame: rt_render_samples_async per shard, records of `rec` bytes.
+// The same buffers and events (slot 0); the ordering edges are render()'s.
+int render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets, int samples,
+                   const double *weights, int fmt, size_t rec, uint8_t *out, int out_on_device,
+                   rt_radiance_stats *stats) {
+  const int n = (int)g->m.size(), dev0 = g->m[0].device;
+  rt_rows rows;
+  int rc = rt_rows_for_shard(H, g->band, 0, n, &rows);
+  if (rc != RT_OK) return rc;
+  const int R = rows.count;
+  const size_t row_bytes = (size_t)W * rec;
+  const size_t shard_bytes = (size_t)R * row_bytes, image_bytes = (size_t)H * row_bytes;
+  for (Member &mb : g->m) {
+    GRP_TRY(g, hipSetDevice(mb.device));
+    if ((rc = grow(g, mb.shard[0], shard_bytes)) != RT_OK) return rc;
+  }
+  GRP_TRY(g, hipSetDevice(dev0));
+  if ((rc = grow(g, g->stage[0], shard_bytes * n)) != RT_OK) return rc;
+  if (!out_on_device && (rc = grow(g, g->image[0], image_bytes)) != RT_OK) return rc;
+  uint8_t *const image = out_on_device ? out : g->image[0].p;
+
+  for (int i = 0; i < n; i++) {
+    Member &mb = g->m[i];
+    if ((rc = rt_rows_for_shard(H, g->band, i, n, &rows)) != RT_OK) return rc;
+    if ((rc = rt_render_samples_async(mb.ctx, cam, W, H, depth, &rows, offsets, samples, weights, fmt,
+                                      mb.shard[0].p)) != RT_OK)
+      return member_fail(g, i, rc, "rt_render_samples_async");
+    GRP_TRY(g, hipSetDevice(mb.device));
+    GRP_TRY(g, hipMemcpyPeerAsync(g->stage[0].p + (size_t)i * shard_bytes, dev0, mb.shard[0].p, mb.device,
+                                  shard_bytes, mb.stream));
+    GRP_TRY(g, hipEventRecord(mb.done[0], mb.stream));
+  }
+  GRP_TRY(g, hipSetDevice(dev0));
+  for (int i = 0; i < n; i++) {
+    GRP_TRY(g, hipStreamWaitEvent(g->assembly, g->m[i].done[0], 0));
+    hipLaunchKernelGGL(place_rows_kernel, dim3((unsigned)R), dim3(kPlaceBlock), 0, g->assembly,
+                       g->stage[0].p + (size_t)i * shard_bytes, image, row_bytes, H, g->band, n, i, R);
+    GRP_TRY(g, hipGetLastError());
+  }
+  if (!out_on_device) GRP_TRY(g, hipMemcpyAsync(out, image, image_bytes, hipMemcpyDeviceToHost, g->assembly));
+  GRP_TRY(g, hipStreamSynchronize(g->assembly));
+
+  rt_radiance_stats sum{};
+  for (int i = 0; i < n; i++) {
+    // Shard i's first row is image row i * band: without it the member launched nothing, and its
+    // report is an earlier call's.
+    if ((long long)i * g->band >= H) continue;
+    rt_radiance_stats st{};
+    if ((rc = rt_radiance_stats_get(g->m[i].ctx, &st)) != RT_OK) return member_fail(g, i, rc, "rt_radiance_stats_get");
+    sum.rays += st.rays;
+    sum.segments += st.segments;
+    sum.hits += st.hits;
+    sum.shadow_rays += st.shadow_rays;
+    sum.tests_exact += st.tests_exact;
+    sum.tests_cull += st.tests_cull;
+    sum.unaccelerated += st.unaccelerated;
+    sum.negative_clamped += st.negative_clamped;
     sum.kernel_ms = std::max(sum.kernel_ms, st.kernel_ms);
   }
   if (stats) *stats = sum;
@@ -489,6 +579,29 @@ int rt_group_render(rt_group *g, const rt_camera *cam, int W, int H, int depth, 
   if (!g->has_scene) return RT_ERR_NO_SCENE;
   if (depth > RT_MAX_DEPTH) return RT_ERR_DEPTH;
   const int rc = render(g, cam, W, H, depth, out, out_on_device, stats);
+  if (rc != RT_OK) drain(g);
+  return rc;
+}
+
+int rt_group_render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets,
+                            int samples, const double *weights, int fmt, void *out, int out_on_device,
+                            rt_radiance_stats *stats) {
+  if (!g || !cam || !offsets || !out || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
+  // what sizes the group's buffers, checked here; the member calls check it again with everything else
+  const size_t rec = fmt == RT_FB_RGB8 ? 3 : fmt == RT_FB_F32X3 ? 12 : fmt == RT_FB_F64X3 ? 24 : 0;
+  if (rec == 0 || samples < 1 || samples > RT_MAX_SAMPLES ||
+      (out_on_device && (reinterpret_cast<uintptr_t>(out) & 15u))) {
+    g->err = rec == 0 ? "rt_group_render_samples: unknown fb_format"
+             : samples < 1 || samples > RT_MAX_SAMPLES ? "rt_group_render_samples: samples outside 1..RT_MAX_SAMPLES"
+                                                       : "rt_group_render_samples: device out is not 16-byte aligned";
+    return RT_ERR_INVALID_ARG;
+  }
+  if (!g->has_scene) {
+    g->err = "rt_group_render_samples: no scene uploaded";
+    return RT_ERR_NO_SCENE;
+  }
+  const int rc = render_samples(g, cam, W, H, depth, offsets, samples, weights, fmt, rec, static_cast<uint8_t *>(out),
+                                out_on_device, stats);
   if (rc != RT_OK) drain(g);
   return rc;
 }

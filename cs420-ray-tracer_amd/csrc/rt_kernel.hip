@@ -1817,7 +1817,7 @@ struct BuildInfo {
 // The launch state of one family of caller-ray queries.  rt_ctx keeps one per
 // family -- the ray queries (rt_trace_rays), the path queries (rt_trace_paths)
 // and the radiance queries (rt_trace_radiance, rt_trace_radiance_resolve,
-// rt_render_samples) -- and nothing of one is shared with another or with the
+// rt_render_samples, rt_render_samples_async) -- and nothing of one is shared with another or with the
 // renders: each has its own counters, its own most recent launch and its own
 // staging.  Created by the family's first launch of a context (trace_state).
 struct TraceState {
@@ -3679,10 +3679,33 @@ struct ResolveSpec {
   const double *weights;  // host, samples of them; nullptr: the box filter
 };
 
+// What the fused launch adds to a resolving launch (rt_render_samples_async): the view its lanes form
+// their rays from.  `rows` holds the real output rows only.
+struct GenSpec {
+  const rt_camera *cam;
+  int W, H;
+  Rows rows;
+  const double *offsets;  // host, 2 * samples of them
+};
+
+// Bytes of reflection stack per one-wave workgroup of a launch at `depth` (> 1).
+static size_t radiance_stack_per_wave(int depth) { return (size_t)64 * (size_t)(depth - 1) * sizeof(StackEnt); }
+
+// The one-wave workgroups of a radiance launch of n lanes' worth of records: the reflection stack belongs
+// to the launch's lane slots, so the grid bounds it, not n; depth 1 spawns nothing and takes none.
+static long long radiance_grid(const rt_ctx *c, size_t n, int depth) {
+  long long grid = trace_grid(c, n);
+  if (depth > 1)
+    grid = std::min<long long>(
+        grid, std::max<long long>(1, (long long)(kRadianceStackBudget / radiance_stack_per_wave(depth))));
+  return grid;
+}
+
 // One radiance launch, validated by its entry point: n records from n rays (rv == nullptr,
-// radiance_kernel<false>) or from n * rv->samples rays (radiance_kernel<true>).
+// radiance_kernel<false>), from n * rv->samples rays (radiance_kernel<true>) or, with `gen`, from
+// n * rv->samples rays the lanes form themselves (radiance_kernel<true, true>; rays == nullptr).
 static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out,
-                           const ResolveSpec *rv) {
+                           const ResolveSpec *rv, const GenSpec *gen = nullptr) {
   int rc;
   RT_TRY(c, hipSetDevice(c->device));
   TraceState &rs = c->radiance;
@@ -3695,13 +3718,9 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
   size_t lds = walk_lds(a.q.bv);
   a.park_off = (int)lds;  // the wave's parked colours behind the walks' stacks
   lds += 64 * sizeof(D3);
-  long long grid = trace_grid(c, n);
-  // the reflection stack belongs to the launch's lane slots, so the grid bounds it, not n; depth 1
-  // spawns nothing and takes none
+  const long long grid = radiance_grid(c, n, depth);
   if (depth > 1) {
-    const size_t per_wave = (size_t)64 * (size_t)(depth - 1) * sizeof(StackEnt);
-    grid = std::min<long long>(grid, std::max<long long>(1, (long long)(kRadianceStackBudget / per_wave)));
-    if ((rc = grow(c, rs.stack, (size_t)grid * per_wave)) != RT_OK) return rc;
+    if ((rc = grow(c, rs.stack, (size_t)grid * radiance_stack_per_wave(depth))) != RT_OK) return rc;
     a.stack = rs.stack.get();
   }
   a.sstride = (unsigned)grid * 64u;
@@ -3710,14 +3729,27 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       hipLaunchKernelGGL(radiance_kernel<false>, dim3((unsigned)grid), dim3(64), lds, c->stream, a);
       return;
     }
-    ResolveArgs ra{};
-    ra.r = a;
-    ra.samples = rv->samples;
-    ra.mode = rv->weights ? kResolveWeighted : rv->samples == 1 ? kResolveSingle : kResolveBox;
+    auto resolve_args = [&](ResolveArgs &ra) {
+      ra.r = a;
+      ra.samples = rv->samples;
+      ra.mode = rv->weights ? kResolveWeighted : rv->samples == 1 ? kResolveSingle : kResolveBox;
+      ra.inv = 1.0 / (double)rv->samples;
+      for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
+    };
     lds += 64 * sizeof(D3);  // the wave's accumulators, right behind its parked colours
-    ra.inv = 1.0 / (double)rv->samples;
-    for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
-    hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
+    if (!gen) {
+      ResolveArgs ra{};
+      resolve_args(ra);
+      hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
+      return;
+    }
+    GenArgs ga{};
+    resolve_args(ga);
+    ga.cam = to_cam(*gen->cam);
+    ga.W = gen->W, ga.H = gen->H, ga.rows = gen->rows;
+    std::memcpy(ga.xy, gen->offsets, (size_t)rv->samples * 2 * sizeof(double));  // by value: free on return
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds, c->stream,
+                       ga);
   });
 }
 
@@ -3806,6 +3838,20 @@ int rt_trace_radiance_resolve(rt_ctx *c, const rt_ray *rays, size_t n, int sampl
   });
 }
 
+// The rows of the image among the output rows of `r`: a prefix (y grows with k), the padding rows
+// their suffix.  The first k with row_y(k) >= H.
+static int real_rows(const Rows &r, int H) {
+  auto row_y = [&](int k) {
+    return (long long)(k / r.band) * r.band * r.stride + (long long)r.first * r.band + (k % r.band);
+  };
+  int lo = 0, hi = r.count;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (row_y(mid) < H) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // The ray buffer of rt_render_samples when the caller names no bound: a choice, 4 Mi rays
 // ("Samples", has the sweep).
 constexpr size_t kSampleRayBytes = 256u << 20;
@@ -3828,16 +3874,7 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   if (!out || (on_device && (reinterpret_cast<uintptr_t>(out) & 15u))) return RT_ERR_INVALID_ARG;
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
   RT_TRY(c, hipSetDevice(c->device));
-  // the rows of the image: a prefix of the output rows (y grows with k), the padding rows their suffix
-  auto row_y = [&](int k) {
-    return (long long)(k / r.band) * r.band * r.stride + (long long)r.first * r.band + (k % r.band);
-  };
-  int lo = 0, hi = r.count;  // the first k with row_y(k) >= H
-  while (lo < hi) {
-    const int mid = lo + (hi - lo) / 2;
-    if (row_y(mid) < H) lo = mid + 1; else hi = mid;
-  }
-  const int real = lo;
+  const int real = real_rows(r, H);
   const size_t cap = max_ray_bytes ? max_ray_bytes : kSampleRayBytes;
   long long chunk = std::max<long long>(1, (long long)(cap / ((size_t)row_rays * sizeof(rt_ray))));
   chunk = std::min<long long>(chunk, (long long)INT32_MAX / row_rays);
@@ -3875,6 +3912,47 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
     *st = rt_radiance_stats{};
     radiance_stats_of(sum, st);
   }
+  return RT_OK;
+}
+
+// rt_render_samples without its ray buffer, and so without its chunks and host waits: the real rows are
+// one radiance_kernel<true, true> launch whose lanes form their pixels' sample rays, the padding rows one
+// memset behind it.
+int rt_render_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
+                            const double *offsets, int samples, const double *weights, int fmt, void *out) {
+  const Rows r = to_rows(rows, H);
+  int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
+  if (rc != RT_OK) return rc;
+  if ((long long)W * samples > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // rt_render_samples' row limit
+  if ((long long)r.count * W > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // one launch: its pixels
+  const size_t rec = radiance_record(fmt);
+  if (rec == 0) return RT_ERR_INVALID_ARG;
+  if ((rc = depth_status(depth)) != RT_OK) return rc;
+  if (r.count == 0) return RT_OK;
+  if (!out || (reinterpret_cast<uintptr_t>(out) & 15u)) return RT_ERR_INVALID_ARG;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  const int real = real_rows(r, H);
+  const size_t npx = (size_t)real * W;
+  if (npx) {
+    // The kernel counts per lane in 32 bits and adds up per wave in 64.  A lane makes `trips` grid-stride
+    // trips of `samples` chains of at most `depth` segments, each with at most one shadow ray per light;
+    // its largest counter (the unaccelerated segments and shadow rays) stays below this product.
+    const long long lanes = radiance_grid(c, npx, depth) * 64;
+    const long long trips = ((long long)npx + lanes - 1) / lanes;  // <= 2^25
+    const long long per_trip = (long long)samples * depth * (1 + (long long)c->scene.nlight);  // < 2^12 * 2^32
+    if (per_trip > (long long)UINT32_MAX / trips) return RT_ERR_INVALID_ARG;
+  }
+  uint8_t *dst = static_cast<uint8_t *>(out);
+  if (npx) {
+    const ResolveSpec rv{samples, weights};
+    const GenSpec gen{cam, W, H, Rows{r.band, r.first, r.stride, real}, offsets};
+    if ((rc = radiance_launch(c, nullptr, npx, depth, fmt, dst, &rv, &gen)) != RT_OK) return rc;
+  } else {
+    RT_TRY(c, hipSetDevice(c->device));
+  }
+  // padding rows: not traced, not counted, zero bytes
+  const size_t pad = (size_t)(r.count - real) * W * rec;
+  if (pad) RT_TRY(c, hipMemsetAsync(dst + npx * rec, 0, pad, c->stream));
   return RT_OK;
 }
 

@@ -39,13 +39,32 @@ struct ResolveArgs {
   double w[RT_MAX_SAMPLES];
 };
 static_assert(offsetof(ResolveArgs, r) == 0, "radiance_kernel reads a ResolveArgs' launch through its first member");
-template <bool kResolve>
+
+// The fused launch (rt_render_samples_async): a resolving launch whose lanes form their sample rays
+// themselves, camera_sample_rays_kernel's arithmetic (rt_query.h) in place of its records.  r.q.nrays
+// counts the pixels of the REAL output rows of `rows` (the padding rows are a suffix, which the host
+// zeroes), r.q.rays is unused.  All of it is wave-uniform and read from the kernel arguments.  A
+// ResolveArgs by inheritance: the kernel's `ka.samples`, `ka.mode`, `ka.w` and its cast to RadianceArgs
+// are the same text for both resolving forms.
+struct GenArgs : ResolveArgs {
+  Cam cam;
+  int W, H;
+  Rows rows;
+  double xy[2 * RT_MAX_SAMPLES];  // (ox_s, oy_s)
+};
+static_assert(sizeof(GenArgs) <= 4096, "the kernel argument segment of a launch");
+
+template <bool kResolve, bool kGen>
 struct RadianceLaunch {
   using Args = RadianceArgs;
 };
 template <>
-struct RadianceLaunch<true> {
+struct RadianceLaunch<true, false> {
   using Args = ResolveArgs;
+};
+template <>
+struct RadianceLaunch<true, true> {
+  using Args = GenArgs;
 };
 
 // path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
@@ -84,9 +103,19 @@ struct RadianceLaunch<true> {
 // the template.  Two details keep it so (each was tried the other way and moved the code): the
 // launch is read through a cast, not a helper returning a reference; a chain's colour `res` keeps
 // its scope and is copied to `pix` for the store.
-template <bool kResolve>
+//
+// kGen (rt_render_samples_async, DESIGN.md section 5b, "Samples, fused and on a group"): the resolving
+// form with sample s's ray formed in the lane from its pixel, the camera and the sample's offsets, all
+// read wave-uniformly from the kernel arguments, instead of loaded -- camera_sample_rays_kernel's
+// direction, normalised once there and once more here as the loaded one is.  Pixel p is column p % W of
+// output row p / W of the launch's rt_rows; the division is written once per trip and (x, j) held across
+// the samples as two ints (written inside the sample loop it compiles to the same instructions and the
+// same resource summary: 53 spilled VGPRs either way).  Everything after the ray is kResolve's.  With
+// kGen false nothing of it is emitted: the two loading forms' assembly is the parent's, line for line.
+template <bool kResolve, bool kGen = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(
-    const typename RadianceLaunch<kResolve>::Args ka) {
+    const typename RadianceLaunch<kResolve, kGen>::Args ka) {
+  static_assert(kResolve || !kGen, "the generating form resolves");
   const RadianceArgs &a = reinterpret_cast<const RadianceArgs &>(ka);  // ResolveArgs::r, at offset 0
   const PathArgs &q = a.q;
   const int lane = (int)(threadIdx.x & 63);
@@ -105,13 +134,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
       nsamp = ka.samples;
       if (ka.mode != kResolveSingle) park[64 + lane] = mk(0.0, 0.0, 0.0);
     }
+    [[maybe_unused]] int gx = 0, gj = 0;  // kGen: the pixel's column and reference row (main.cpp:74)
+    if constexpr (kGen) {
+      const int p = (int)ld, k = p / ka.W;  // ld < nrays <= 2^31-1
+      const Rows &rw = ka.rows;
+      const long long y =
+          (long long)(k / rw.band) * rw.band * rw.stride + (long long)rw.first * rw.band + (k % rw.band);
+      gx = p - k * ka.W;
+      gj = ka.H - 1 - (int)y;  // a real row: y < H
+    }
     D3 pix;
     int s = 0;
     do {  // the pixel's samples; the body keeps the level loop's indentation
-    const long long ri = kResolve ? ld * nsamp + s : ld;
-    const double2 r0 = src[ri * 4 + 0], r1 = src[ri * 4 + 1], r2 = src[ri * 4 + 2];
-    D3 o = mk(r0.x, r0.y, r1.x);
-    D3 d = normalized(mk(r1.y, r2.x, r2.y));  // Ray(o, d), ray.h:12: once
+    D3 o, d;
+    if constexpr (kGen) {
+      const D3 dir = normalized(
+          camera_dir(ka.cam, (double)gx + ka.xy[2 * s], (double)gj + ka.xy[2 * s + 1], ka.W, ka.H));  // the record's
+      o = mk(ka.cam.px, ka.cam.py, ka.cam.pz);
+      d = normalized(dir);  // Ray(o, d) on the record's direction: once more
+    } else {
+      const long long ri = kResolve ? ld * nsamp + s : ld;
+      const double2 r0 = src[ri * 4 + 0], r1 = src[ri * 4 + 1], r2 = src[ri * 4 + 2];
+      o = mk(r0.x, r0.y, r1.x);
+      d = normalized(mk(r1.y, r2.x, r2.y));  // Ray(o, d), ray.h:12: once
+    }
     bool alive = act;
     int key = -1;  // the sphere the ray leaves: groups the sweeps' lanes, changes no result
     int lev = 0;   // stack entries this lane holds

@@ -17,7 +17,9 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   trace_ray's skeleton   src/main.cpp:16-58              -> Renderer.trace_paths (hits, shadow masks, reflections)
   trace_ray              src/main.cpp:16-58              -> Renderer.trace_radiance (colours of the caller's rays)
   the `-a` sample loop   src/main_gpu.cu:249-333         -> Renderer.render_samples, camera_sample_rays,
-                                                            trace_radiance_resolve (a caller's pattern and weights)
+                                                            trace_radiance_resolve (a caller's pattern and weights),
+                                                            Renderer.render_samples_async (one fused launch),
+                                                            Group.render_samples (row-sharded over a group)
 """
 from __future__ import annotations
 
@@ -230,6 +232,11 @@ SIGNATURES = {
     "rt_render_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(rt_rows),
                                     C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int,
                                     C.c_size_t, C.POINTER(rt_radiance_stats)]),
+    "rt_render_samples_async": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(rt_rows),
+                                          C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
+    "rt_group_render_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                          C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int,
+                                          C.POINTER(rt_radiance_stats)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -659,6 +666,18 @@ class Renderer:
                "rt_render_samples", self._ctx, L=self._L)
         return out, st
 
+    def render_samples_async(self, cam: rt_camera, width: int, height: int, depth: int, offsets, out_ptr: int,
+                             weights=None, rows: rt_rows | None = None, fmt: int = RT_FB_RGB8):
+        """rt_render_samples_async: render_samples' records of `rows` (None = the full frame) written
+        at out_ptr (device memory, 16-byte aligned) by one launch that forms its own rays, enqueued
+        on the context's stream; radiance_stats() afterwards reports it."""
+        off, s = _doubles(offsets, 2)
+        w = _sample_weights(weights, s)
+        _check(self._L.rt_render_samples_async(self._ctx, C.byref(cam), width, height, depth,
+                                               C.byref(rows) if rows is not None else None, off, s, w, fmt,
+                                               C.c_void_p(out_ptr)),
+               "rt_render_samples_async", self._ctx, L=self._L)
+
     def close(self):
         if self._ctx:
             self._L.rt_destroy(self._ctx)
@@ -735,6 +754,25 @@ class Group:
         self._check_grp(self._L.rt_group_render_frames(self._grp, arr, n, width, height, depth, batch,
                                                        C.c_void_p(_addr(out)), int(out_on_device), frame_stride,
                                                        C.byref(st)), "rt_group_render_frames")
+        return out, st
+
+    def render_samples(self, cam: rt_camera, width: int, height: int, depth: int, offsets, weights=None,
+                       fmt: int = RT_FB_RGB8, out=None, out_on_device: bool = False):
+        """rt_group_render_samples: Renderer.render_samples of the full frame, sharded as render()
+        shards one.  `out`: None (a host numpy [height * width, 3] array of the format's dtype is
+        made), a host buffer, or with out_on_device a buffer / pointer of devices[0].  Returns
+        (out, rt_radiance_stats): the counts summed over the members, kernel_ms their maximum."""
+        off, s = _doubles(offsets, 2)
+        w = _sample_weights(weights, s)
+        if out is None:
+            import numpy as np
+
+            out = np.zeros((height * width, 3), _fb_dtype(fmt, np.uint8))
+        ptr = out if isinstance(out, int) else _addr(out)
+        st = rt_radiance_stats()
+        self._check_grp(self._L.rt_group_render_samples(self._grp, C.byref(cam), width, height, depth, off, s, w, fmt,
+                                                        C.c_void_p(ptr), int(out_on_device), C.byref(st)),
+                        "rt_group_render_samples")
         return out, st
 
     def member(self, i: int):

@@ -50,6 +50,10 @@
  *   rt_camera_sample_rays / rt_trace_radiance_resolve / rt_trace_radiance_resolve_async / rt_render_samples
  *                                   <- the four-sample loop of ray_gpu's `-a`, src/main_gpu.cu:249-333, for a
  *                                      sample pattern and weights the caller supplies
+ *   rt_render_samples_async         <- (new) rt_render_samples' chunk loop, as one launch that forms its own rays
+ *                                      and only enqueues
+ *   rt_group_render_samples         <- (new) rt_render_samples of a frame, row-sharded over a device group as
+ *                                      rt_group_render shards rt_render
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -86,7 +90,8 @@ extern "C" {
                                    (rt_trace_paths, rt_trace_paths_async, rt_path_stats_get) and the radiance
                                    queries (rt_trace_radiance, rt_trace_radiance_async, rt_radiance_stats_get) and the
                                    multi-sample entries (rt_camera_sample_rays, rt_trace_radiance_resolve,
-                                   rt_trace_radiance_resolve_async, rt_render_samples) */
+                                   rt_trace_radiance_resolve_async, rt_render_samples) and their fused and
+                                   group forms (rt_render_samples_async, rt_group_render_samples) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -583,6 +588,34 @@ int rt_render_samples(rt_ctx *ctx, const rt_camera *cam, int width, int height, 
                       const rt_rows *rows /* NULL = full frame */, const double *offsets_xy, int samples,
                       const double *weights /* nullable */, int fb_format, void *out, int out_on_device,
                       size_t max_ray_bytes /* 0 = default */, rt_radiance_stats *stats /* nullable */);
+/* Replaces rt_render_samples' host loop (a ray-generator launch, a resolving launch and a host wait per
+   chunk of rows) with ONE launch that only enqueues: every lane forms its pixel's sample rays itself, so
+   there is no ray buffer, no chunk and no max_ray_bytes.  Writes to out_device (device memory, 16-byte
+   aligned) exactly the records rt_render_samples(..., out_on_device = 1, ...) writes for the same
+   arguments, bit for bit, in the three formats: the ray arithmetic (rt_camera_sample_rays' direction,
+   normalised once more), the resolve rule, the quantiser, the NaN -> 255 rule and the -0.0 rule of one
+   unweighted sample are the same.
+   The real rows of `rows` (NULL = the full frame) are one radiance launch on the context's current
+   stream; the padding rows, a suffix of the output rows, are not traced or counted and are zeroed by a
+   hipMemsetAsync on the same stream.  The call never waits.  offsets_xy and weights are HOST memory, read
+   during the call and free on return.
+   It uses the radiance queries' events, counters and reflection stack, but not their ray staging, which
+   it neither touches nor grows.  rt_radiance_stats_get afterwards reports this launch for the whole call:
+   rays = real pixels * samples, kernel_ms this one kernel.  A call without a real row launches nothing
+   and leaves that report as it was.  As every radiance launch it changes nothing that rt_render_stats,
+   rt_kernel_times, rt_get_info, rt_trace_stats or rt_path_stats_get report; rt_set_antialias does not
+   apply.
+   Errors, before any HIP call: rt_render_samples' (arguments, width * samples > 2^31-1, the format, the
+   depth, then the scene), and as RT_ERR_INVALID_ARG a NULL or misaligned out_device and
+   rows->count * width > 2^31-1 (the limit is on the pixels of the one launch; the rays may pass 2^31).
+   The kernel counts per lane in 32 bits: a launch in which one lane could pass 2^32-1 --
+   trips * samples * depth * (1 + lights), trips the lane's pixels at the launch's grid (at most 64 waves
+   per CU; 2080 waves at depth 64) -- is RT_ERR_INVALID_ARG as well: on a 256-CU device 2^31-1 pixels of
+   64 samples at depth 64 pass it with up to 63 lights, a 4K frame of them with more than 16,000.
+   rows->count == 0 is RT_OK and a no-op. */
+int rt_render_samples_async(rt_ctx *ctx, const rt_camera *cam, int width, int height, int depth,
+                            const rt_rows *rows /* NULL = full frame */, const double *offsets_xy, int samples,
+                            const double *weights /* nullable */, int fb_format, void *out_device);
 
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
@@ -630,6 +663,22 @@ int  rt_group_render(rt_group *grp, const rt_camera *cam, int width, int height,
 int  rt_group_render_frames(rt_group *grp, const rt_camera *cams, int nframes, int width, int height,
                             int depth, int batch, uint8_t *rgb_out, int out_on_device,
                             size_t frame_stride, rt_stats *stats);
+/* rt_render_samples of the full frame, row-sharded over the members as rt_group_render shards a frame.
+   Synchronous.  out: H*W records in PPM row order, record y*width + x, in host memory or (out_on_device = 1)
+   memory of devices[0], 16-byte aligned: byte for byte what rt_render_samples writes on one context, in
+   the three formats.  rt_group_render's flow: member i enqueues rt_render_samples_async of
+   rt_rows_for_shard(H, band, i, n) into its shard buffer, one hipMemcpyPeerAsync to devices[0], and the
+   assembly stream places the shard's real rows (width * 3, 12 or 24 bytes each) as it arrives; the buffers
+   and events are those of the other two render calls, any of which may follow any other.
+   stats (nullable): counts summed over the members that had a real row, kernel_ms their maximum (a member
+   whose shard is all padding launches nothing).  rt_group_set_antialias does not apply.
+   Errors: a NULL grp, cam, offsets_xy or out and width / height <= 0 are RT_ERR_INVALID_ARG before any
+   HIP call; so are an unknown fb_format, samples outside 1..RT_MAX_SAMPLES and a misaligned device out,
+   with rt_group_last_error set; no uploaded scene is RT_ERR_NO_SCENE; the rest are
+   rt_render_samples_async's, with the member named in rt_group_last_error.  The group stays usable. */
+int  rt_group_render_samples(rt_group *grp, const rt_camera *cam, int width, int height, int depth,
+                             const double *offsets_xy, int samples, const double *weights /* nullable */,
+                             int fb_format, void *out, int out_on_device, rt_radiance_stats *stats /* nullable */);
 
 #ifdef __cplusplus
 }
