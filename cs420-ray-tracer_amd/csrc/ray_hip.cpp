@@ -30,11 +30,18 @@
 // --sample-devices LIST (only with --supersample; not with --gpus, --devices or
 // -a): the supersampled frame as row shards, one per listed device, through the
 // device group (rt_group_render_samples); the same lines, file and --json fields.
+// --aperture R [--focus F] (only with --supersample N; R >= 0): depth of field.
+// Sample s leaves the thin-lens point lens_pattern(N, R)[s] of rt_hip.py (a disk
+// of radius R) towards the plane F along forward, which stays sharp (default: the
+// distance from the scene's camera position to its look-at point), through
+// rt_render_lens_samples, or with --sample-devices rt_group_render_lens_samples.
+// --focus without --aperture is a usage error; without --aperture nothing changes.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,13 +69,15 @@ struct Opts {
   int frames = -1, batch = -1;  // --frames N [--batch B]: a sequence per pass (rt_group_render_frames); -1: not given
   int supersample = 0;  // --supersample N: N x N samples per pixel through rt_render_samples; 0: not given
   std::vector<int> sample_devices;  // --sample-devices LIST: --supersample through rt_group_render_samples
+  bool lens = false, focus_given = false;  // --aperture R [--focus F]: --supersample through rt_render_lens_samples
+  double aperture = 0.0, focus = 0.0;
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a | --supersample N] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
                "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
-               "          [--sample-devices D0,D1,...] [--json] [scene.txt]\n"
+               "          [--sample-devices D0,D1,...] [--aperture R [--focus F]] [--json] [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
                "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
                "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
@@ -76,7 +85,9 @@ int usage(const char *argv0) {
                "  --supersample N N x N box-filtered samples per pixel (1..8); one device: not with --gpus,\n"
                "                  --devices or -a\n"
                "  --sample-devices LIST  with --supersample: the frame's row shards, one per listed device,\n"
-               "                  through the device group; not with --gpus, --devices or -a\n",
+               "                  through the device group; not with --gpus, --devices or -a\n"
+               "  --aperture R    with --supersample: depth of field, a thin lens of radius R >= 0 (scene units);\n"
+               "                  --focus F: the distance of the sharp plane (default: camera to look-at point)\n",
                argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
   return 2;
 }
@@ -136,7 +147,9 @@ int render_single(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8
 }
 
 // --supersample N: the full frame through rt_render_samples, N x N samples per pixel at (a/N, b/N), a fastest;
-// with --sample-devices through rt_group_render_samples on a group of band 8.
+// with --sample-devices through rt_group_render_samples on a group of band 8.  With --aperture R the
+// lens forms of the two calls, sample s at the lens point of grid cell N*N-1-s (rt_hip.py lens_pattern:
+// the same doubles in the same order).
 int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
   const int N = o.supersample;
   std::vector<double> offsets;
@@ -145,6 +158,20 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
       offsets.push_back((double)a / N);
       offsets.push_back((double)b / N);
     }
+  std::vector<double> lens;
+  if (o.lens)
+    for (int s = 0; s < N * N; s++) {
+      const int c = N * N - 1 - s, a = c % N, b = c / N;
+      const double u = (a + 0.5) / N * 2.0 - 1.0, v = (b + 0.5) / N * 2.0 - 1.0;
+      lens.push_back(u * std::sqrt(1.0 - v * v / 2.0) * o.aperture);
+      lens.push_back(v * std::sqrt(1.0 - u * u / 2.0) * o.aperture);
+    }
+  double focus = o.focus;
+  if (o.lens && !o.focus_given) {
+    const double dx = sc.cam_look_at[0] - sc.cam_position[0], dy = sc.cam_look_at[1] - sc.cam_position[1],
+                 dz = sc.cam_look_at[2] - sc.cam_position[2];
+    focus = std::sqrt(dx * dx + dy * dy + dz * dz);
+  }
   rt_radiance_stats st{};
   auto report = [&] {
     res.kernel_ms = st.kernel_ms;
@@ -159,8 +186,10 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
     int rc = rt_group_upload_scene(grp, &sc);
     for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
       auto t0 = std::chrono::high_resolution_clock::now();
-      rc = rt_group_render_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), N * N, nullptr, RT_FB_RGB8,
-                                   img, 0, &st);
+      rc = o.lens ? rt_group_render_lens_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), lens.data(),
+                                                 focus, N * N, nullptr, RT_FB_RGB8, img, 0, &st)
+                  : rt_group_render_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), N * N, nullptr,
+                                            RT_FB_RGB8, img, 0, &st);
       auto t1 = std::chrono::high_resolution_clock::now();
       res.wall_s = std::chrono::duration<double>(t1 - t0).count();
     }
@@ -175,8 +204,12 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
   CK(rt_upload_scene(ctx, &sc));
   for (int it = 0; it < o.repeat; it++) {
     auto t0 = std::chrono::high_resolution_clock::now();
-    CK(rt_render_samples(ctx, &cam, o.width, o.height, o.depth, nullptr, offsets.data(), N * N, nullptr, RT_FB_RGB8,
-                         img, 0, 0, &st));
+    if (o.lens)
+      CK(rt_render_lens_samples(ctx, &cam, o.width, o.height, o.depth, nullptr, offsets.data(), lens.data(), focus,
+                                N * N, nullptr, RT_FB_RGB8, img, 0, &st));
+    else
+      CK(rt_render_samples(ctx, &cam, o.width, o.height, o.depth, nullptr, offsets.data(), N * N, nullptr, RT_FB_RGB8,
+                           img, 0, 0, &st));
     auto t1 = std::chrono::high_resolution_clock::now();
     res.wall_s = std::chrono::duration<double>(t1 - t0).count();
   }
@@ -393,6 +426,12 @@ int main(int argc, char **argv) {
       dst = std::atoi(argv[++i]);
       return true;
     };
+    auto next_double = [&](double &dst) {  // the whole argument, or nothing
+      if (i + 1 >= argc) return false;
+      char *end = nullptr;
+      dst = std::strtod(argv[++i], &end);
+      return end != argv[i] && *end == '\0';
+    };
     if (a == "--openmp") o.openmp_only = true;
     else if (a == "--width") { if (!next(o.width)) return usage(argv[0]); }
     else if (a == "--height") { if (!next(o.height)) return usage(argv[0]); }
@@ -409,6 +448,8 @@ int main(int argc, char **argv) {
     else if (a == "-a") o.samples = 4;
     else if (a == "--supersample") { if (!next(o.supersample) || o.supersample < 1 || o.supersample > 8) return usage(argv[0]); }
     else if (a == "--sample-devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.sample_devices)) return usage(argv[0]); }
+    else if (a == "--aperture") { if (!next_double(o.aperture) || !(o.aperture >= 0.0)) return usage(argv[0]); o.lens = true; }
+    else if (a == "--focus") { if (!next_double(o.focus)) return usage(argv[0]); o.focus_given = true; }
     else if (a == "--json") o.json = true;
     else if (a == "-h" || a == "--help") return usage(argv[0]);
     else o.scene = a;  // any other argument is the scene path, as main.cpp:103-110
@@ -417,6 +458,7 @@ int main(int argc, char **argv) {
   if (!o.devices.empty() && (o.gpus > 1 || o.force_gather)) return usage(argv[0]);
   if (o.supersample && (gpus_given || !o.devices.empty() || o.force_gather || o.samples != 1)) return usage(argv[0]);
   if (!o.sample_devices.empty() && !o.supersample) return usage(argv[0]);  // with --supersample: the line above
+  if ((o.lens && !o.supersample) || (o.focus_given && !o.lens)) return usage(argv[0]);
   if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116

@@ -44,8 +44,9 @@
 //       of batch b-2's iteration -- so no wait can be skipped, and with more
 //       streams than hardware queues no barrier sits in front of the packet
 //       it waits for.
-//   (e) rt_group_render, rt_group_render_samples (rt_group_render's flow with
-//       rt_render_samples_async per shard, records of 3, 12 or 24 bytes and
+//   (e) rt_group_render, rt_group_render_samples and rt_group_render_lens_samples
+//       (rt_group_render's flow with rt_render_samples_async or
+//       rt_render_lens_samples_async per shard, records of 3, 12 or 24 bytes and
 //       place_rows_kernel) and rt_group_render_frames share the buffers and the
 //       events (one frame uses slot 0): all are synchronous and return
 //       with every stream of the group idle -- each member's last work is its
@@ -312,11 +313,12 @@ int render(rt_group *g, const rt_camera *cam, int W, int H, int depth, uint8_t *
   return RT_OK;
 }
 
-// render()'s flow for a multi-sample frame: rt_render_samples_async per shard, records of `rec` bytes.
+// render()'s flow for a multi-sample frame: rt_render_samples_async per shard (with `lens`, the lens
+// points of rt_group_render_lens_samples, rt_render_lens_samples_async), records of `rec` bytes.
 // The same buffers and events (slot 0); the ordering edges are render()'s.
-int render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets, int samples,
-                   const double *weights, int fmt, size_t rec, uint8_t *out, int out_on_device,
-                   rt_radiance_stats *stats) {
+int render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets,
+                   const double *lens, double focus, int samples, const double *weights, int fmt, size_t rec,
+                   uint8_t *out, int out_on_device, rt_radiance_stats *stats) {
   const int n = (int)g->m.size(), dev0 = g->m[0].device;
   rt_rows rows;
   int rc = rt_rows_for_shard(H, g->band, 0, n, &rows);
@@ -336,9 +338,11 @@ int render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, c
   for (int i = 0; i < n; i++) {
     Member &mb = g->m[i];
     if ((rc = rt_rows_for_shard(H, g->band, i, n, &rows)) != RT_OK) return rc;
-    if ((rc = rt_render_samples_async(mb.ctx, cam, W, H, depth, &rows, offsets, samples, weights, fmt,
-                                      mb.shard[0].p)) != RT_OK)
-      return member_fail(g, i, rc, "rt_render_samples_async");
+    rc = lens ? rt_render_lens_samples_async(mb.ctx, cam, W, H, depth, &rows, offsets, lens, focus, samples, weights,
+                                             fmt, mb.shard[0].p)
+              : rt_render_samples_async(mb.ctx, cam, W, H, depth, &rows, offsets, samples, weights, fmt,
+                                        mb.shard[0].p);
+    if (rc != RT_OK) return member_fail(g, i, rc, lens ? "rt_render_lens_samples_async" : "rt_render_samples_async");
     GRP_TRY(g, hipSetDevice(mb.device));
     GRP_TRY(g, hipMemcpyPeerAsync(g->stage[0].p + (size_t)i * shard_bytes, dev0, mb.shard[0].p, mb.device,
                                   shard_bytes, mb.stream));
@@ -583,27 +587,44 @@ int rt_group_render(rt_group *g, const rt_camera *cam, int W, int H, int depth, 
   return rc;
 }
 
-int rt_group_render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets,
-                            int samples, const double *weights, int fmt, void *out, int out_on_device,
-                            rt_radiance_stats *stats) {
+// rt_group_render_samples and, with `lens`, rt_group_render_lens_samples (`name` in the error texts).
+static int group_render_samples(rt_group *g, const char *name, const rt_camera *cam, int W, int H, int depth,
+                                const double *offsets, const double *lens, double focus, int samples,
+                                const double *weights, int fmt, void *out, int out_on_device,
+                                rt_radiance_stats *stats) {
   if (!g || !cam || !offsets || !out || W <= 0 || H <= 0) return RT_ERR_INVALID_ARG;
   // what sizes the group's buffers, checked here; the member calls check it again with everything else
   const size_t rec = fmt == RT_FB_RGB8 ? 3 : fmt == RT_FB_F32X3 ? 12 : fmt == RT_FB_F64X3 ? 24 : 0;
   if (rec == 0 || samples < 1 || samples > RT_MAX_SAMPLES ||
       (out_on_device && (reinterpret_cast<uintptr_t>(out) & 15u))) {
-    g->err = rec == 0 ? "rt_group_render_samples: unknown fb_format"
-             : samples < 1 || samples > RT_MAX_SAMPLES ? "rt_group_render_samples: samples outside 1..RT_MAX_SAMPLES"
-                                                       : "rt_group_render_samples: device out is not 16-byte aligned";
+    g->err = std::string(name) + (rec == 0 ? ": unknown fb_format"
+                                  : samples < 1 || samples > RT_MAX_SAMPLES ? ": samples outside 1..RT_MAX_SAMPLES"
+                                                                            : ": device out is not 16-byte aligned");
     return RT_ERR_INVALID_ARG;
   }
   if (!g->has_scene) {
-    g->err = "rt_group_render_samples: no scene uploaded";
+    g->err = std::string(name) + ": no scene uploaded";
     return RT_ERR_NO_SCENE;
   }
-  const int rc = render_samples(g, cam, W, H, depth, offsets, samples, weights, fmt, rec, static_cast<uint8_t *>(out),
-                                out_on_device, stats);
+  const int rc = render_samples(g, cam, W, H, depth, offsets, lens, focus, samples, weights, fmt, rec,
+                                static_cast<uint8_t *>(out), out_on_device, stats);
   if (rc != RT_OK) drain(g);
   return rc;
+}
+
+int rt_group_render_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets,
+                            int samples, const double *weights, int fmt, void *out, int out_on_device,
+                            rt_radiance_stats *stats) {
+  return group_render_samples(g, "rt_group_render_samples", cam, W, H, depth, offsets, nullptr, 0.0, samples, weights,
+                              fmt, out, out_on_device, stats);
+}
+
+int rt_group_render_lens_samples(rt_group *g, const rt_camera *cam, int W, int H, int depth, const double *offsets,
+                                 const double *lens, double focus, int samples, const double *weights, int fmt,
+                                 void *out, int out_on_device, rt_radiance_stats *stats) {
+  if (!lens) return RT_ERR_INVALID_ARG;
+  return group_render_samples(g, "rt_group_render_lens_samples", cam, W, H, depth, offsets, lens, focus, samples,
+                              weights, fmt, out, out_on_device, stats);
 }
 
 int rt_group_render_frames(rt_group *g, const rt_camera *cams, int nframes, int W, int H, int depth, int batch,

@@ -1817,7 +1817,8 @@ struct BuildInfo {
 // The launch state of one family of caller-ray queries.  rt_ctx keeps one per
 // family -- the ray queries (rt_trace_rays), the path queries (rt_trace_paths)
 // and the radiance queries (rt_trace_radiance, rt_trace_radiance_resolve,
-// rt_render_samples, rt_render_samples_async) -- and nothing of one is shared with another or with the
+// rt_render_samples, rt_render_samples_async, rt_render_lens_samples[_async])
+// -- and nothing of one is shared with another or with the
 // renders: each has its own counters, its own most recent launch and its own
 // staging.  Created by the family's first launch of a context (trace_state).
 struct TraceState {
@@ -3686,6 +3687,8 @@ struct GenSpec {
   int W, H;
   Rows rows;
   const double *offsets;  // host, 2 * samples of them
+  const double *lens;     // host, 2 * samples lens points: radiance_kernel<true, true, true>; nullptr: the pinhole
+  double focus;           // with `lens`: the distance of the plane that stays sharp
 };
 
 // Bytes of reflection stack per one-wave workgroup of a launch at `depth` (> 1).
@@ -3703,7 +3706,8 @@ static long long radiance_grid(const rt_ctx *c, size_t n, int depth) {
 
 // One radiance launch, validated by its entry point: n records from n rays (rv == nullptr,
 // radiance_kernel<false>), from n * rv->samples rays (radiance_kernel<true>) or, with `gen`, from
-// n * rv->samples rays the lanes form themselves (radiance_kernel<true, true>; rays == nullptr).
+// n * rv->samples rays the lanes form themselves (radiance_kernel<true, true>, or with gen->lens
+// radiance_kernel<true, true, true>; rays == nullptr).
 static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out,
                            const ResolveSpec *rv, const GenSpec *gen = nullptr) {
   int rc;
@@ -3743,13 +3747,25 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
       return;
     }
-    GenArgs ga{};
-    resolve_args(ga);
-    ga.cam = to_cam(*gen->cam);
-    ga.W = gen->W, ga.H = gen->H, ga.rows = gen->rows;
-    std::memcpy(ga.xy, gen->offsets, (size_t)rv->samples * 2 * sizeof(double));  // by value: free on return
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds, c->stream,
-                       ga);
+    auto gen_args = [&](GenArgs &ga) {
+      resolve_args(ga);
+      ga.cam = to_cam(*gen->cam);
+      ga.W = gen->W, ga.H = gen->H, ga.rows = gen->rows;
+      std::memcpy(ga.xy, gen->offsets, (size_t)rv->samples * 2 * sizeof(double));  // by value: free on return
+    };
+    if (!gen->lens) {
+      GenArgs ga{};
+      gen_args(ga);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds,
+                         c->stream, ga);
+      return;
+    }
+    LensArgs la{};
+    gen_args(la);
+    la.focus = gen->focus;
+    std::memcpy(la.lens, gen->lens, (size_t)rv->samples * 2 * sizeof(double));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true>), dim3((unsigned)grid), dim3(64), lds,
+                       c->stream, la);
   });
 }
 
@@ -3815,6 +3831,28 @@ int rt_camera_sample_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const r
   if (total == 0) return RT_OK;
   RT_TRY(c, hipSetDevice(c->device));
   return sample_rays_launch(c, cam, W, H, r, 0, r.count, offsets, samples, rays);
+}
+
+int rt_camera_lens_rays(rt_ctx *c, const rt_camera *cam, int W, int H, const rt_rows *rows, const double *offsets,
+                        const double *lens, double focus, int samples, rt_ray *rays) {
+  if (!rays || !lens || (reinterpret_cast<uintptr_t>(rays) & 15u)) return RT_ERR_INVALID_ARG;
+  const Rows r = to_rows(rows, H);
+  const int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
+  if (rc != RT_OK) return rc;
+  const long long total = (long long)r.count * W * samples;  // < 2^31 * 2^31 * 2^6
+  if (total > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
+  if (total == 0) return RT_OK;
+  RT_TRY(c, hipSetDevice(c->device));
+  SampleOffsets off{};
+  SampleLens ln{};
+  std::memcpy(off.xy, offsets, (size_t)samples * 2 * sizeof(double));  // by value: the caller's arrays are free on return
+  std::memcpy(ln.xy, lens, (size_t)samples * 2 * sizeof(double));
+  ln.focus = focus;
+  const unsigned grid = (unsigned)((total + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(camera_lens_rays_kernel, dim3(grid), dim3(kBlock), 0, c->stream, to_cam(*cam), W, H, r, samples,
+                     off, ln, rays);
+  RT_TRY(c, hipGetLastError());
+  return RT_OK;
 }
 
 int rt_trace_radiance_resolve_async(rt_ctx *c, const rt_ray *rays, size_t n, int samples, const double *weights,
@@ -3915,23 +3953,21 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   return RT_OK;
 }
 
-// rt_render_samples without its ray buffer, and so without its chunks and host waits: the real rows are
-// one radiance_kernel<true, true> launch whose lanes form their pixels' sample rays, the padding rows one
-// memset behind it.
-int rt_render_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
-                            const double *offsets, int samples, const double *weights, int fmt, void *out) {
-  const Rows r = to_rows(rows, H);
+// What the fused calls check before any HIP call, in rt_render_samples' order; `align`: out is device
+// memory.  real: the real rows of r.  r.count == 0 returns RT_OK with nothing else checked.
+static int fused_validate(const rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const Rows &r,
+                          const double *offsets, int samples, int fmt, const void *out, bool align, int &real) {
+  real = 0;
   int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
   if (rc != RT_OK) return rc;
   if ((long long)W * samples > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // rt_render_samples' row limit
   if ((long long)r.count * W > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // one launch: its pixels
-  const size_t rec = radiance_record(fmt);
-  if (rec == 0) return RT_ERR_INVALID_ARG;
+  if (radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
   if ((rc = depth_status(depth)) != RT_OK) return rc;
   if (r.count == 0) return RT_OK;
-  if (!out || (reinterpret_cast<uintptr_t>(out) & 15u)) return RT_ERR_INVALID_ARG;
+  if (!out || (align && (reinterpret_cast<uintptr_t>(out) & 15u))) return RT_ERR_INVALID_ARG;
   if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
-  const int real = real_rows(r, H);
+  real = real_rows(r, H);
   const size_t npx = (size_t)real * W;
   if (npx) {
     // The kernel counts per lane in 32 bits and adds up per wave in 64.  A lane makes `trips` grid-stride
@@ -3942,10 +3978,20 @@ int rt_render_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int d
     const long long per_trip = (long long)samples * depth * (1 + (long long)c->scene.nlight);  // < 2^12 * 2^32
     if (per_trip > (long long)UINT32_MAX / trips) return RT_ERR_INVALID_ARG;
   }
+  return RT_OK;
+}
+
+// A validated fused call, r.count > 0: the real rows are one launch whose lanes form their pixels' sample
+// rays (through the lens when `lens` is given), the padding rows one memset behind it.  Only enqueues.
+static int fused_enqueue(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const Rows &r, int real,
+                         const double *offsets, const double *lens, double focus, int samples,
+                         const double *weights, int fmt, void *out) {
+  int rc;
+  const size_t rec = radiance_record(fmt), npx = (size_t)real * W;
   uint8_t *dst = static_cast<uint8_t *>(out);
   if (npx) {
     const ResolveSpec rv{samples, weights};
-    const GenSpec gen{cam, W, H, Rows{r.band, r.first, r.stride, real}, offsets};
+    const GenSpec gen{cam, W, H, Rows{r.band, r.first, r.stride, real}, offsets, lens, focus};
     if ((rc = radiance_launch(c, nullptr, npx, depth, fmt, dst, &rv, &gen)) != RT_OK) return rc;
   } else {
     RT_TRY(c, hipSetDevice(c->device));
@@ -3954,6 +4000,59 @@ int rt_render_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int d
   const size_t pad = (size_t)(r.count - real) * W * rec;
   if (pad) RT_TRY(c, hipMemsetAsync(dst + npx * rec, 0, pad, c->stream));
   return RT_OK;
+}
+
+// rt_render_samples without its ray buffer, and so without its chunks and host waits: the real rows are
+// one radiance_kernel<true, true> launch whose lanes form their pixels' sample rays, the padding rows one
+// memset behind it.
+int rt_render_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
+                            const double *offsets, int samples, const double *weights, int fmt, void *out) {
+  const Rows r = to_rows(rows, H);
+  int real;
+  const int rc = fused_validate(c, cam, W, H, depth, r, offsets, samples, fmt, out, true, real);
+  if (rc != RT_OK || r.count == 0) return rc;
+  return fused_enqueue(c, cam, W, H, depth, r, real, offsets, nullptr, 0.0, samples, weights, fmt, out);
+}
+
+// rt_render_samples_async through a thin lens: radiance_kernel<true, true, true>.
+int rt_render_lens_samples_async(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
+                                 const double *offsets, const double *lens, double focus, int samples,
+                                 const double *weights, int fmt, void *out) {
+  if (!lens) return RT_ERR_INVALID_ARG;
+  const Rows r = to_rows(rows, H);
+  int real;
+  const int rc = fused_validate(c, cam, W, H, depth, r, offsets, samples, fmt, out, true, real);
+  if (rc != RT_OK || r.count == 0) return rc;
+  return fused_enqueue(c, cam, W, H, depth, r, real, offsets, lens, focus, samples, weights, fmt, out);
+}
+
+// The synchronous form: the fused launch where `out` is (device memory) or into the family's grow-only
+// `out` staging with one copy back behind it (host memory), then one wait.
+int rt_render_lens_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, const rt_rows *rows,
+                           const double *offsets, const double *lens, double focus, int samples,
+                           const double *weights, int fmt, void *out, int on_device, rt_radiance_stats *st) {
+  if (!lens) return RT_ERR_INVALID_ARG;
+  const Rows r = to_rows(rows, H);
+  int real, rc = fused_validate(c, cam, W, H, depth, r, offsets, samples, fmt, out, on_device != 0, real);
+  if (rc != RT_OK) return rc;
+  if (st) *st = rt_radiance_stats{};
+  if (r.count == 0) return RT_OK;
+  RT_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)r.count * W * radiance_record(fmt);
+  void *dev = out;
+  if (!on_device) {
+    if ((rc = grow(c, c->radiance.out[0], bytes)) != RT_OK) return rc;
+    dev = c->radiance.out[0].get();
+  }
+  if ((rc = fused_enqueue(c, cam, W, H, depth, r, real, offsets, lens, focus, samples, weights, fmt, dev)) != RT_OK)
+    return rc;
+  if (!on_device) RT_TRY(c, hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (real == 0) {  // nothing launched: the family's report is an earlier call's
+    RT_TRY(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+  }
+  rt_radiance_stats tmp;
+  return rt_radiance_stats_get(c, st ? st : &tmp);
 }
 
 int rt_kernel_times(rt_ctx *c, double *ms_out, int max_n, int *n_out) {

@@ -163,4 +163,49 @@ __global__ __launch_bounds__(kBlock) void camera_sample_rays_kernel(const Cam ca
   dst[3] = make_double2(__builtin_inf(), 0.0);
 }
 
+// A thin lens in front of camera_dir: the ray of one sample leaves the lens point P + right*lx + up*ly
+// and passes through the point P + dir0*focus of the focal plane, where dir0 (camera_dir's unnormalised
+// direction, forward component 1) is the pinhole ray of the sample.  Returns the record's direction,
+// normalised once, and the record's origin in `o`.  (lx, ly) = (0, 0) and focus = 1.0 give the pinhole
+// record as values: o = P + 0, dir = normalized(dir0*1 - 0).  Any double is allowed: a non-finite lens
+// point or focus gives NaN rays, which the queries treat as misses.  rt_camera_lens_rays and
+// radiance_kernel's kLens form share it.
+__device__ __forceinline__ D3 lens_ray(const Cam &cam, D3 dir0, double lx, double ly, double focus, D3 &o) {
+  const D3 lv = add(scale(mk(cam.rx, cam.ry, cam.rz), lx), scale(mk(cam.ux, cam.uy, cam.uz), ly));
+  o = add(mk(cam.px, cam.py, cam.pz), lv);
+  return normalized(sub(scale(dir0, focus), lv));
+}
+
+// rt_camera_lens_rays: camera_sample_rays_kernel with the lens.  The same layout and padding rows; the
+// lens points travel in the kernel arguments beside the offsets, sample s pairing offset s with lens
+// point s.  One thread per ray.
+struct SampleLens {
+  double focus;
+  double xy[2 * RT_MAX_SAMPLES];  // (lx_s, ly_s)
+};
+__global__ __launch_bounds__(kBlock) void camera_lens_rays_kernel(const Cam cam, int W, int H, const Rows rows, int S,
+                                                                   const SampleOffsets off, const SampleLens lens,
+                                                                   rt_ray *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long long)rows.count * W * S) return;
+  const int s = (int)(i % S);
+  const long long p = i / S;
+  const int k = (int)(p / W), x = (int)(p % W);
+  const long long y = (long long)(k / rows.band) * rows.band * rows.stride + (long long)rows.first * rows.band +
+                      (k % rows.band);
+  double2 *dst = reinterpret_cast<double2 *>(out) + i * 4;
+  if (y >= H) {  // padding rows of a shard
+    dst[0] = dst[1] = dst[2] = dst[3] = make_double2(0.0, 0.0);
+    return;
+  }
+  const int j = H - 1 - (int)y;  // reference row (main.cpp:74)
+  const D3 dir0 = camera_dir(cam, (double)x + off.xy[2 * s], (double)j + off.xy[2 * s + 1], W, H);
+  D3 o;
+  const D3 d = lens_ray(cam, dir0, lens.xy[2 * s], lens.xy[2 * s + 1], lens.focus, o);
+  dst[0] = make_double2(o.x, o.y);
+  dst[1] = make_double2(o.z, d.x);
+  dst[2] = make_double2(d.y, d.z);
+  dst[3] = make_double2(__builtin_inf(), 0.0);
+}
+
 }  // namespace rtk

@@ -54,17 +54,30 @@ struct GenArgs : ResolveArgs {
 };
 static_assert(sizeof(GenArgs) <= 4096, "the kernel argument segment of a launch");
 
-template <bool kResolve, bool kGen>
+// The fused launch through a thin lens (rt_render_lens_samples_async): GenArgs and, per sample, the
+// point of the lens its ray leaves from, in scene units along the camera's right and up, and per launch
+// the distance along forward of the plane that stays sharp.  Wave-uniform, read from the kernel arguments.
+struct LensArgs : GenArgs {
+  double focus;
+  double lens[2 * RT_MAX_SAMPLES];  // (lx_s, ly_s)
+};
+static_assert(sizeof(LensArgs) <= 4096, "the kernel argument segment of a launch");
+
+template <bool kResolve, bool kGen, bool kLens>
 struct RadianceLaunch {
   using Args = RadianceArgs;
 };
 template <>
-struct RadianceLaunch<true, false> {
+struct RadianceLaunch<true, false, false> {
   using Args = ResolveArgs;
 };
 template <>
-struct RadianceLaunch<true, true> {
+struct RadianceLaunch<true, true, false> {
   using Args = GenArgs;
+};
+template <>
+struct RadianceLaunch<true, true, true> {
+  using Args = LensArgs;
 };
 
 // path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
@@ -112,10 +125,17 @@ struct RadianceLaunch<true, true> {
 // the samples as two ints (written inside the sample loop it compiles to the same instructions and the
 // same resource summary: 53 spilled VGPRs either way).  Everything after the ray is kResolve's.  With
 // kGen false nothing of it is emitted: the two loading forms' assembly is the parent's, line for line.
-template <bool kResolve, bool kGen = false>
+//
+// kLens (rt_render_lens_samples_async, DESIGN.md section 5b, "Samples through a lens"): kGen with sample
+// s's ray leaving the lens point P + right*lx_s + up*ly_s towards the point of the focal plane the
+// pinhole ray meets, camera_lens_rays_kernel's arithmetic (rt_query.h).  The origin becomes a per-lane
+// value; the lens points and the focus distance are read wave-uniformly as the offsets are.  Only the ray
+// formation differs, and with kLens false none of it is emitted.
+template <bool kResolve, bool kGen = false, bool kLens = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(
-    const typename RadianceLaunch<kResolve, kGen>::Args ka) {
+    const typename RadianceLaunch<kResolve, kGen, kLens>::Args ka) {
   static_assert(kResolve || !kGen, "the generating form resolves");
+  static_assert(kGen || !kLens, "the lens form generates");
   const RadianceArgs &a = reinterpret_cast<const RadianceArgs &>(ka);  // ResolveArgs::r, at offset 0
   const PathArgs &q = a.q;
   const int lane = (int)(threadIdx.x & 63);
@@ -147,7 +167,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
     int s = 0;
     do {  // the pixel's samples; the body keeps the level loop's indentation
     D3 o, d;
-    if constexpr (kGen) {
+    if constexpr (kLens) {
+      const D3 dir0 = camera_dir(ka.cam, (double)gx + ka.xy[2 * s], (double)gj + ka.xy[2 * s + 1], ka.W, ka.H);
+      const D3 dir = lens_ray(ka.cam, dir0, ka.lens[2 * s], ka.lens[2 * s + 1], ka.focus, o);  // the record's
+      d = normalized(dir);  // Ray(o, d) on the record's direction: once more
+    } else if constexpr (kGen) {
       const D3 dir = normalized(
           camera_dir(ka.cam, (double)gx + ka.xy[2 * s], (double)gj + ka.xy[2 * s + 1], ka.W, ka.H));  // the record's
       o = mk(ka.cam.px, ka.cam.py, ka.cam.pz);

@@ -20,6 +20,9 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
                                                             trace_radiance_resolve (a caller's pattern and weights),
                                                             Renderer.render_samples_async (one fused launch),
                                                             Group.render_samples (row-sharded over a group)
+  a pinhole only         include/camera.h:17-25          -> Renderer.camera_lens_rays, render_lens_samples[_async],
+                                                            Group.render_lens_samples, lens_pattern (a thin lens:
+                                                            depth of field for the multi-sample renders)
 """
 from __future__ import annotations
 
@@ -237,6 +240,19 @@ SIGNATURES = {
     "rt_group_render_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                           C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int,
                                           C.POINTER(rt_radiance_stats)]),
+    "rt_camera_lens_rays": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.POINTER(rt_rows),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, _P]),
+    "rt_render_lens_samples_async": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(rt_rows), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
+    "rt_render_lens_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.POINTER(rt_rows),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                         C.POINTER(C.c_double), C.c_int, _P, C.c_int,
+                                         C.POINTER(rt_radiance_stats)]),
+    "rt_group_render_lens_samples": (C.c_int, [_P, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                               C.POINTER(C.c_double), C.c_int, _P, C.c_int,
+                                               C.POINTER(rt_radiance_stats)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -678,6 +694,53 @@ class Renderer:
                                                C.c_void_p(out_ptr)),
                "rt_render_samples_async", self._ctx, L=self._L)
 
+    def camera_lens_rays(self, cam: rt_camera, width: int, height: int, rows: rt_rows | None, offsets, lens,
+                         focus: float, rays_ptr: int):
+        """rt_camera_lens_rays: camera_sample_rays through a thin lens.  Sample s leaves the lens point
+        lens[s] ((lx, ly) pairs in scene units along the camera's right and up, e.g. lens_pattern(n, r))
+        towards the point its pinhole ray meets on the plane `focus` along forward."""
+        off, s = _doubles(offsets, 2)
+        ln = _lens_points(lens, s)
+        _check(self._L.rt_camera_lens_rays(self._ctx, C.byref(cam), width, height,
+                                           C.byref(rows) if rows is not None else None, off, ln, float(focus), s,
+                                           C.c_void_p(rays_ptr)),
+               "rt_camera_lens_rays", self._ctx, L=self._L)
+
+    def render_lens_samples(self, cam: rt_camera, width: int, height: int, depth: int, offsets, lens, focus: float,
+                            weights=None, rows: rt_rows | None = None, fmt: int = RT_FB_RGB8, out=None,
+                            out_on_device: bool = False):
+        """rt_render_lens_samples: render_samples with depth of field, as one fused launch.  `lens`:
+        one (lx, ly) pair per offset; `focus`: the distance of the plane that stays sharp.  `out` as
+        render_samples'.  Returns (out, stats), the stats that one launch's."""
+        off, s = _doubles(offsets, 2)
+        ln = _lens_points(lens, s)
+        w = _sample_weights(weights, s)
+        count = rows.count if rows is not None else height
+        if out is None:
+            import numpy as np
+
+            out = np.zeros((max(count, 0) * width, 3), _fb_dtype(fmt, np.uint8))
+        ptr = out if isinstance(out, int) else _addr(out)
+        st = rt_radiance_stats()
+        _check(self._L.rt_render_lens_samples(self._ctx, C.byref(cam), width, height, depth,
+                                              C.byref(rows) if rows is not None else None, off, ln, float(focus), s,
+                                              w, fmt, C.c_void_p(ptr), int(out_on_device), C.byref(st)),
+               "rt_render_lens_samples", self._ctx, L=self._L)
+        return out, st
+
+    def render_lens_samples_async(self, cam: rt_camera, width: int, height: int, depth: int, offsets, lens,
+                                  focus: float, out_ptr: int, weights=None, rows: rt_rows | None = None,
+                                  fmt: int = RT_FB_RGB8):
+        """rt_render_lens_samples_async: render_samples_async through the lens of render_lens_samples,
+        enqueued on the context's stream; radiance_stats() afterwards reports it."""
+        off, s = _doubles(offsets, 2)
+        ln = _lens_points(lens, s)
+        w = _sample_weights(weights, s)
+        _check(self._L.rt_render_lens_samples_async(self._ctx, C.byref(cam), width, height, depth,
+                                                    C.byref(rows) if rows is not None else None, off, ln,
+                                                    float(focus), s, w, fmt, C.c_void_p(out_ptr)),
+               "rt_render_lens_samples_async", self._ctx, L=self._L)
+
     def close(self):
         if self._ctx:
             self._L.rt_destroy(self._ctx)
@@ -775,6 +838,25 @@ class Group:
                         "rt_group_render_samples")
         return out, st
 
+    def render_lens_samples(self, cam: rt_camera, width: int, height: int, depth: int, offsets, lens, focus: float,
+                            weights=None, fmt: int = RT_FB_RGB8, out=None, out_on_device: bool = False):
+        """rt_group_render_lens_samples: Renderer.render_lens_samples of the full frame, sharded as
+        render_samples shards one; `out` and the return value as render_samples'."""
+        off, s = _doubles(offsets, 2)
+        ln = _lens_points(lens, s)
+        w = _sample_weights(weights, s)
+        if out is None:
+            import numpy as np
+
+            out = np.zeros((height * width, 3), _fb_dtype(fmt, np.uint8))
+        ptr = out if isinstance(out, int) else _addr(out)
+        st = rt_radiance_stats()
+        self._check_grp(self._L.rt_group_render_lens_samples(self._grp, C.byref(cam), width, height, depth, off, ln,
+                                                             float(focus), s, w, fmt, C.c_void_p(ptr),
+                                                             int(out_on_device), C.byref(st)),
+                        "rt_group_render_lens_samples")
+        return out, st
+
     def member(self, i: int):
         """The borrowed rt_ctx of member i (rt_group_member)."""
         ctx = self._L.rt_group_member(self._grp, i)
@@ -808,6 +890,35 @@ def grid_pattern(n: int) -> list[tuple[float, float]]:
     if n < 1:
         raise ValueError(f"grid_pattern({n})")
     return [(a / n, b / n) for b in range(n) for a in range(n)]
+
+
+def lens_pattern(n: int, aperture: float) -> list[tuple[float, float]]:
+    """The n x n lens points that go with grid_pattern(n): a lens disk of radius `aperture` (scene
+    units).  Sample s takes grid cell n*n-1-s (reversed, so that a sample's pixel offset and its lens
+    point are not aligned); the cell is (a, b), a fastest, its centre (u, v) = ((a+.5)/n*2-1,
+    (b+.5)/n*2-1) in the square [-1, 1]^2, mapped to the unit disk as (u*sqrt(1 - v*v/2),
+    v*sqrt(1 - u*u/2)) and multiplied by `aperture`.  Only correctly rounded operations, in this
+    order: ray_hip --aperture computes the same doubles."""
+    if n < 1:
+        raise ValueError(f"lens_pattern({n})")
+    import math
+
+    pts = []
+    for s in range(n * n):
+        c = n * n - 1 - s
+        a, b = c % n, c // n
+        u = (a + 0.5) / n * 2.0 - 1.0
+        v = (b + 0.5) / n * 2.0 - 1.0
+        pts.append((u * math.sqrt(1.0 - v * v / 2.0) * aperture, v * math.sqrt(1.0 - u * u / 2.0) * aperture))
+    return pts
+
+
+def _lens_points(lens, samples: int):
+    """The `lens_xy` argument of the lens calls: one (lx, ly) pair per sample."""
+    ln, n = _doubles(lens, 2)
+    if n != samples:
+        raise ValueError(f"{n} lens points for {samples} samples")
+    return ln
 
 
 def _doubles(values, width: int):

@@ -54,6 +54,11 @@
  *                                      and only enqueues
  *   rt_group_render_samples         <- (new) rt_render_samples of a frame, row-sharded over a device group as
  *                                      rt_group_render shards rt_render
+ *   rt_camera_lens_rays / rt_render_lens_samples_async / rt_render_lens_samples / rt_group_render_lens_samples
+ *                                   <- (new) a caller's own camera kernel for depth of field (the reference has
+ *                                      a pinhole only, include/camera.h:17-25): rt_camera_sample_rays,
+ *                                      rt_render_samples_async, rt_render_samples and rt_group_render_samples
+ *                                      with each sample's ray leaving a point of a thin lens
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -91,7 +96,9 @@ extern "C" {
                                    queries (rt_trace_radiance, rt_trace_radiance_async, rt_radiance_stats_get) and the
                                    multi-sample entries (rt_camera_sample_rays, rt_trace_radiance_resolve,
                                    rt_trace_radiance_resolve_async, rt_render_samples) and their fused and
-                                   group forms (rt_render_samples_async, rt_group_render_samples) */
+                                   group forms (rt_render_samples_async, rt_group_render_samples) and the
+                                   thin-lens forms (rt_camera_lens_rays, rt_render_lens_samples_async,
+                                   rt_render_lens_samples, rt_group_render_lens_samples) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -617,6 +624,52 @@ int rt_render_samples_async(rt_ctx *ctx, const rt_camera *cam, int width, int he
                             const rt_rows *rows /* NULL = full frame */, const double *offsets_xy, int samples,
                             const double *weights /* nullable */, int fb_format, void *out_device);
 
+/* ---- samples through a thin lens (depth of field) ---------------------------
+   One definition for the four entries below.  Per sample s the caller gives the pixel offset (ox_s, oy_s)
+   as above and a LENS POINT (lx_s, ly_s) = lens_xy[2s], lens_xy[2s+1], in scene units along cam->right and
+   cam->up; per call one FOCUS distance, along cam->forward from cam->position to the plane that stays
+   sharp.  With P = cam->position, R = cam->right, U = cam->up and no contraction:
+     dir0 = camera_dir(cam, (double)x + ox_s, (double)j + oy_s, W, H)    unnormalised, forward component 1
+     lv   = R*lx_s + U*ly_s
+     o    = P + lv                                                       the record's origin
+     dir  = normalized(dir0*focus - lv)                                  the record's direction
+   and the record is {o, dir, tmax = +inf, reserved = 0}; a query normalises dir once more, as Ray() does.
+   Rays of one pixel and offset from different lens points meet at P + dir0*focus.  Sample s pairs offset s
+   with lens point s: decorrelating the two is the caller's job.  Any double is allowed: a non-finite lens
+   point or focus gives NaN rays, which the queries treat as misses; it is never an error.  With every lens
+   point (0, 0) and focus = 1.0 the rays are rt_camera_sample_rays' as values (a zero component may differ
+   in sign).  lens_xy is HOST memory, 2*samples doubles, read during the call and free on return. */
+
+/* Replaces a caller's own lens-camera kernel (or host loop) in front of the radiance queries:
+   rt_camera_sample_rays with the lens.  The same layout (rays[(k*width + x)*samples + s]), the same
+   all-zero rays for padding rows, asynchronous on the context's stream, needs no scene.
+   Errors: rt_camera_sample_rays'; a NULL lens_xy is RT_ERR_INVALID_ARG as well. */
+int rt_camera_lens_rays(rt_ctx *ctx, const rt_camera *cam, int width, int height, const rt_rows *rows,
+                        const double *offsets_xy /* host, 2*samples doubles */,
+                        const double *lens_xy /* host, 2*samples doubles */, double focus, int samples,
+                        rt_ray *rays_device);
+/* Replaces rt_camera_lens_rays into a ray buffer of the caller's (64 bytes per sample, chunked by the
+   caller) followed by rt_trace_radiance_resolve_async: rt_render_samples_async with the lens.  ONE launch,
+   no ray buffer, never waits.  Writes to out_device exactly the records that pair of calls writes, bit for
+   bit, in the three formats.  Everything else is rt_render_samples_async's: the padding rows zeroed by a
+   hipMemsetAsync, the radiance family's events, counters and reflection stack and none of its staging, the
+   report of rt_radiance_stats_get, the order of the errors and the 32-bit per-lane counter check (the lens
+   changes no trip, sample, depth or light count).  A NULL lens_xy is RT_ERR_INVALID_ARG as well. */
+int rt_render_lens_samples_async(rt_ctx *ctx, const rt_camera *cam, int width, int height, int depth,
+                                 const rt_rows *rows /* NULL = full frame */, const double *offsets_xy,
+                                 const double *lens_xy, double focus, int samples,
+                                 const double *weights /* nullable */, int fb_format, void *out_device);
+/* Replaces rt_render_lens_samples_async, a device-to-host copy and a wait written by the caller: the
+   synchronous form.  out is host memory or (out_on_device = 1) device memory, 16-byte aligned.  The fused
+   launch, for host memory into the radiance family's grow-only `out` staging with one hipMemcpyAsync back,
+   and ONE wait.  There is no max_ray_bytes: there is no ray buffer.  stats (nullable) are that launch's
+   (rt_radiance_stats_get's); zeros when no row of `rows` is real or rows->count == 0.
+   Errors: rt_render_lens_samples_async's, the alignment of out only for device memory. */
+int rt_render_lens_samples(rt_ctx *ctx, const rt_camera *cam, int width, int height, int depth,
+                           const rt_rows *rows /* NULL = full frame */, const double *offsets_xy,
+                           const double *lens_xy, double focus, int samples, const double *weights /* nullable */,
+                           int fb_format, void *out, int out_on_device, rt_radiance_stats *stats /* nullable */);
+
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
  * streams and shard buffers, ncclGather to device 0, rt_unpermute_rows -- with
@@ -679,6 +732,16 @@ int  rt_group_render_frames(rt_group *grp, const rt_camera *cams, int nframes, i
 int  rt_group_render_samples(rt_group *grp, const rt_camera *cam, int width, int height, int depth,
                              const double *offsets_xy, int samples, const double *weights /* nullable */,
                              int fb_format, void *out, int out_on_device, rt_radiance_stats *stats /* nullable */);
+/* Replaces a caller's own sharding of rt_render_lens_samples_async over devices: rt_group_render_samples
+   with the lens (the section "samples through a thin lens" above).  Per member the fused lens call on its
+   shard; the same buffers, events, placement kernel and stats rule, and byte for byte what
+   rt_render_lens_samples writes on one context.  It may follow or precede the other three group render
+   calls in any order.  Errors: rt_group_render_samples'; a NULL lens_xy is RT_ERR_INVALID_ARG before any
+   HIP call as well. */
+int  rt_group_render_lens_samples(rt_group *grp, const rt_camera *cam, int width, int height, int depth,
+                                  const double *offsets_xy, const double *lens_xy, double focus, int samples,
+                                  const double *weights /* nullable */, int fb_format, void *out,
+                                  int out_on_device, rt_radiance_stats *stats /* nullable */);
 
 #ifdef __cplusplus
 }
