@@ -36,6 +36,11 @@
 // distance from the scene's camera position to its look-at point), through
 // rt_render_lens_samples, or with --sample-devices rt_group_render_lens_samples.
 // --focus without --aperture is a usage error; without --aperture nothing changes.
+// --light-radius R (only with --supersample N; R >= 0; with or without --aperture and
+// --sample-devices): area lights, soft shadows.  Sample s sees light l moved by
+// light_pattern(N, R, num_lights)[s][l] of rt_hip.py (a horizontal disk of radius
+// R), set once through rt_set_light_samples, or rt_group_set_light_samples, ahead
+// of the render.  Without --light-radius nothing changes.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -71,13 +76,16 @@ struct Opts {
   std::vector<int> sample_devices;  // --sample-devices LIST: --supersample through rt_group_render_samples
   bool lens = false, focus_given = false;  // --aperture R [--focus F]: --supersample through rt_render_lens_samples
   double aperture = 0.0, focus = 0.0;
+  bool area = false;  // --light-radius R: --supersample under rt_set_light_samples
+  double light_radius = 0.0;
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a | --supersample N] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
                "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
-               "          [--sample-devices D0,D1,...] [--aperture R [--focus F]] [--json] [scene.txt]\n"
+               "          [--sample-devices D0,D1,...] [--aperture R [--focus F]] [--light-radius R] [--json]\n"
+               "          [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
                "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
                "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
@@ -87,7 +95,9 @@ int usage(const char *argv0) {
                "  --sample-devices LIST  with --supersample: the frame's row shards, one per listed device,\n"
                "                  through the device group; not with --gpus, --devices or -a\n"
                "  --aperture R    with --supersample: depth of field, a thin lens of radius R >= 0 (scene units);\n"
-               "                  --focus F: the distance of the sharp plane (default: camera to look-at point)\n",
+               "                  --focus F: the distance of the sharp plane (default: camera to look-at point)\n"
+               "  --light-radius R  with --supersample: area lights, each light a horizontal disk of radius R >= 0\n"
+               "                  (scene units) sampled once per pixel sample: soft shadows\n",
                argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
   return 2;
 }
@@ -149,7 +159,8 @@ int render_single(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8
 // --supersample N: the full frame through rt_render_samples, N x N samples per pixel at (a/N, b/N), a fastest;
 // with --sample-devices through rt_group_render_samples on a group of band 8.  With --aperture R the
 // lens forms of the two calls, sample s at the lens point of grid cell N*N-1-s (rt_hip.py lens_pattern:
-// the same doubles in the same order).
+// the same doubles in the same order).  With --light-radius R the light table of rt_hip.py
+// light_pattern(N, R, num_lights), restated the same way, is set ahead of the render.
 int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
   const int N = o.supersample;
   std::vector<double> offsets;
@@ -158,14 +169,33 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
       offsets.push_back((double)a / N);
       offsets.push_back((double)b / N);
     }
+  // point s of lens_pattern(N, radius): the centre of grid cell N*N-1-s on the disk of that radius
+  auto disk_point = [N](int s, double radius, double &x, double &y) {
+    const int c = N * N - 1 - s, a = c % N, b = c / N;
+    const double u = (a + 0.5) / N * 2.0 - 1.0, v = (b + 0.5) / N * 2.0 - 1.0;
+    x = u * std::sqrt(1.0 - v * v / 2.0) * radius;
+    y = v * std::sqrt(1.0 - u * u / 2.0) * radius;
+  };
   std::vector<double> lens;
   if (o.lens)
     for (int s = 0; s < N * N; s++) {
-      const int c = N * N - 1 - s, a = c % N, b = c / N;
-      const double u = (a + 0.5) / N * 2.0 - 1.0, v = (b + 0.5) / N * 2.0 - 1.0;
-      lens.push_back(u * std::sqrt(1.0 - v * v / 2.0) * o.aperture);
-      lens.push_back(v * std::sqrt(1.0 - u * u / 2.0) * o.aperture);
+      double x, y;
+      disk_point(s, o.aperture, x, y);
+      lens.push_back(x);
+      lens.push_back(y);
     }
+  std::vector<double> light_xyz;  // [s][l]: point (s + 17 l) % (N*N) of the disk, as (x, 0, z)
+  if (o.area) {
+    for (int s = 0; s < N * N; s++)
+      for (int l = 0; l < sc.num_lights; l++) {
+        double x, z;
+        disk_point((s + 17 * l) % (N * N), o.light_radius, x, z);
+        light_xyz.push_back(x);
+        light_xyz.push_back(0.0);
+        light_xyz.push_back(z);
+      }
+    if (light_xyz.empty()) light_xyz.push_back(0.0);  // a scene without lights: a non-NULL, empty table
+  }
   double focus = o.focus;
   if (o.lens && !o.focus_given) {
     const double dx = sc.cam_look_at[0] - sc.cam_position[0], dy = sc.cam_look_at[1] - sc.cam_position[1],
@@ -184,6 +214,7 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
     rt_group *grp = nullptr;
     CK(rt_group_create(o.sample_devices.data(), (int)o.sample_devices.size(), 8, &grp));
     int rc = rt_group_upload_scene(grp, &sc);
+    if (rc == RT_OK && o.area) rc = rt_group_set_light_samples(grp, light_xyz.data(), N * N);
     for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
       auto t0 = std::chrono::high_resolution_clock::now();
       rc = o.lens ? rt_group_render_lens_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), lens.data(),
@@ -202,6 +233,7 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
   rt_ctx *ctx = nullptr;
   CK(rt_create(o.device, &ctx));
   CK(rt_upload_scene(ctx, &sc));
+  if (o.area) CK(rt_set_light_samples(ctx, light_xyz.data(), N * N));
   for (int it = 0; it < o.repeat; it++) {
     auto t0 = std::chrono::high_resolution_clock::now();
     if (o.lens)
@@ -449,6 +481,7 @@ int main(int argc, char **argv) {
     else if (a == "--supersample") { if (!next(o.supersample) || o.supersample < 1 || o.supersample > 8) return usage(argv[0]); }
     else if (a == "--sample-devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.sample_devices)) return usage(argv[0]); }
     else if (a == "--aperture") { if (!next_double(o.aperture) || !(o.aperture >= 0.0)) return usage(argv[0]); o.lens = true; }
+    else if (a == "--light-radius") { if (!next_double(o.light_radius) || !(o.light_radius >= 0.0)) return usage(argv[0]); o.area = true; }
     else if (a == "--focus") { if (!next_double(o.focus)) return usage(argv[0]); o.focus_given = true; }
     else if (a == "--json") o.json = true;
     else if (a == "-h" || a == "--help") return usage(argv[0]);
@@ -459,6 +492,7 @@ int main(int argc, char **argv) {
   if (o.supersample && (gpus_given || !o.devices.empty() || o.force_gather || o.samples != 1)) return usage(argv[0]);
   if (!o.sample_devices.empty() && !o.supersample) return usage(argv[0]);  // with --supersample: the line above
   if ((o.lens && !o.supersample) || (o.focus_given && !o.lens)) return usage(argv[0]);
+  if (o.area && !o.supersample) return usage(argv[0]);
   if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116

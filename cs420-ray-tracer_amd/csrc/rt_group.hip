@@ -567,6 +567,23 @@ int rt_group_upload_scene(rt_group *g, const rt_scene *scene) {
   return RT_OK;
 }
 
+int rt_group_set_light_samples(rt_group *g, const double *light_xyz, int samples) {
+  if (!g) return RT_ERR_INVALID_ARG;
+  if (light_xyz && (samples < 1 || samples > RT_MAX_SAMPLES)) {
+    g->err = "rt_group_set_light_samples: samples outside 1..RT_MAX_SAMPLES";
+    return RT_ERR_INVALID_ARG;
+  }
+  if (!g->has_scene) {
+    g->err = "rt_group_set_light_samples: no scene uploaded";
+    return RT_ERR_NO_SCENE;
+  }
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    const int rc = rt_set_light_samples(g->m[i].ctx, light_xyz, samples);
+    if (rc != RT_OK) return member_fail(g, i, rc, "rt_set_light_samples");
+  }
+  return RT_OK;
+}
+
 int rt_group_set_antialias(rt_group *g, int samples) {
   if (!g || (samples != 1 && samples != 4)) return RT_ERR_INVALID_ARG;
   for (int i = 0; i < (int)g->m.size(); i++) {
@@ -605,6 +622,15 @@ static int group_render_samples(rt_group *g, const char *name, const rt_camera *
   if (!g->has_scene) {
     g->err = std::string(name) + ": no scene uploaded";
     return RT_ERR_NO_SCENE;
+  }
+  // the members' light tables (rt_group_set_light_samples): the member calls would refuse too, without a text
+  for (const Member &mb : g->m) {
+    const int table = rt_light_samples(mb.ctx);
+    if (table != 0 && table != samples) {
+      g->err = std::string(name) + ": samples (" + std::to_string(samples) + ") differs from the light table's (" +
+               std::to_string(table) + ", rt_group_set_light_samples)";
+      return RT_ERR_INVALID_ARG;
+    }
   }
   const int rc = render_samples(g, cam, W, H, depth, offsets, lens, focus, samples, weights, fmt, rec,
                                 static_cast<uint8_t *>(out), out_on_device, stats);

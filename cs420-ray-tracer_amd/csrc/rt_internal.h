@@ -23,4 +23,7 @@ RT_INTERNAL int rt_add_counts(rt_ctx *ctx, unsigned long long *acc_device);
 // history of rt_kernel_times as it is.
 RT_INTERNAL int rt_launch_ms(rt_ctx *ctx, long long index, double *ms);
 
+// The sample count of the context's light table (rt_set_light_samples); 0 without one.  No HIP call.
+RT_INTERNAL int rt_light_samples(const rt_ctx *ctx);
+
 #endif  // RT_INTERNAL_H

@@ -1575,6 +1575,7 @@ struct Scene {
   DevBuf<double> rad;  // |radius|, for the conservative cull only
   DevBuf<SphMat> mat;
   DevBuf<LightD> lights;
+  std::vector<LightD> lights_host;  // the uploaded records: what rt_set_light_samples shifts
   int nsph = 0, nlight = 0;
   double amb[3] = {0, 0, 0};
   double c0[3] = {0, 0, 0};
@@ -1830,6 +1831,11 @@ struct TraceState {
   // the synchronous calls from host memory: the batch on the device, and what it
   // answers (hits; vertices and surfaces; colour records)
   DevBuf<uint8_t> rays, out[2];
+  // radiance only: the light table of the resolving launches (rt_set_light_samples), [area_samples][nlight]
+  // shifted copies of the scene's light records; area_samples == 0: no table.  Replaced or cleared only with
+  // the stream idle (the setter, rt_upload_scene).
+  DevBuf<LightD> area;
+  int area_samples = 0;
 };
 
 struct rt_ctx {
@@ -3340,6 +3346,7 @@ static int upload_staged(rt_ctx *c, const rt_scene *s, StagedScene &st, bool wan
   RT_TRY(c, scn.rad.upload(st.rad, 1));
   RT_TRY(c, scn.mat.upload(st.mat, 1));
   RT_TRY(c, scn.lights.upload(st.lights, 1));
+  scn.lights_host = st.lights;
   // built on the device from geo / rad
   int rc = light_grids(c, s, st);
   if (rc != RT_OK) return rc;
@@ -3364,6 +3371,8 @@ int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   RT_TRY(c, hipSetDevice(c->device));
   RT_TRY(c, hipStreamSynchronize(c->stream));
   free_scene(c);
+  c->radiance.area.reset();  // the light table goes with the scene: the light count may change
+  c->radiance.area_samples = 0;
   const bool big = s->num_spheres > kBvhAlwaysAbove;
   // leaves of 2 spheres (+0.6..0.9 % over 4 on synth200 with the merged levels);
   // 1 above kBvhAlwaysAbove, where every closest hit walks (synth10k 4.37 -> 4.16 ms)
@@ -3666,6 +3675,42 @@ static int radiance_validate(const rt_ctx *c, const void *rays, size_t n, int sa
   return RT_OK;
 }
 
+// The light table of the resolving launches: record s * nl + l is the uploaded light l with its position
+// moved by the caller's offset, one fp64 add per component, formed here so that the kernel only reads.
+int rt_set_light_samples(rt_ctx *c, const double *xyz, int samples) {
+  if (!c) return RT_ERR_INVALID_ARG;
+  if (xyz && (samples < 1 || samples > RT_MAX_SAMPLES)) return RT_ERR_INVALID_ARG;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));  // work in flight may read the table being replaced
+  TraceState &rs = c->radiance;
+  if (!xyz) {
+    rs.area.reset();
+    rs.area_samples = 0;
+    return RT_OK;
+  }
+  const std::vector<LightD> &src = c->scene.lights_host;
+  const size_t nl = src.size();
+  std::vector<LightD> rec((size_t)samples * nl);
+  for (size_t s = 0; s < (size_t)samples; s++)
+    for (size_t l = 0; l < nl; l++) {
+      const double *o = xyz + (s * nl + l) * 3;
+      LightD L = src[l];
+      L.px = L.px + o[0], L.py = L.py + o[1], L.pz = L.pz + o[2];
+      rec[s * nl + l] = L;
+    }
+  DevBuf<LightD> next;  // the previous table stays in force if this fails
+  RT_TRY(c, next.upload(rec, 1));
+  rs.area = std::move(next);
+  rs.area_samples = samples;
+  return RT_OK;
+}
+
+// `samples` of a resolving call against the light table's, where a table is set: they agree.
+static bool light_table_mismatch(const rt_ctx *c, int samples) {
+  return c->radiance.area_samples != 0 && c->radiance.area_samples != samples;
+}
+
 // The most reflection-stack scratch a radiance launch takes.  A launch of
 // `grid` one-wave workgroups at `depth` needs grid * 64 * (depth - 1) entries
 // of 32 bytes: 32 MiB per level below the first for the full grid of 64 waves
@@ -3707,7 +3752,8 @@ static long long radiance_grid(const rt_ctx *c, size_t n, int depth) {
 // One radiance launch, validated by its entry point: n records from n rays (rv == nullptr,
 // radiance_kernel<false>), from n * rv->samples rays (radiance_kernel<true>) or, with `gen`, from
 // n * rv->samples rays the lanes form themselves (radiance_kernel<true, true>, or with gen->lens
-// radiance_kernel<true, true, true>; rays == nullptr).
+// radiance_kernel<true, true, true>; rays == nullptr).  A resolving launch of a context with a light table
+// (and lights) is the same form's kArea instantiation, its argument block followed by the table's address.
 static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out,
                            const ResolveSpec *rv, const GenSpec *gen = nullptr) {
   int rc;
@@ -3741,10 +3787,17 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
     };
     lds += 64 * sizeof(D3);  // the wave's accumulators, right behind its parked colours
+    const LightD *area = rs.area_samples != 0 && c->scene.nlight > 0 ? rs.area.get() : nullptr;
     if (!gen) {
-      ResolveArgs ra{};
+      AreaArgs<ResolveArgs> ra{};
       resolve_args(ra);
-      hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream, ra);
+      ra.area = area;
+      if (area)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, false, false, true>), dim3((unsigned)grid), dim3(64),
+                           lds, c->stream, ra);
+      else
+        hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream,
+                           static_cast<const ResolveArgs &>(ra));
       return;
     }
     auto gen_args = [&](GenArgs &ga) {
@@ -3754,18 +3807,28 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       std::memcpy(ga.xy, gen->offsets, (size_t)rv->samples * 2 * sizeof(double));  // by value: free on return
     };
     if (!gen->lens) {
-      GenArgs ga{};
+      AreaArgs<GenArgs> ga{};
       gen_args(ga);
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds,
-                         c->stream, ga);
+      ga.area = area;
+      if (area)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, false, true>), dim3((unsigned)grid), dim3(64),
+                           lds, c->stream, ga);
+      else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds,
+                           c->stream, static_cast<const GenArgs &>(ga));
       return;
     }
-    LensArgs la{};
+    AreaArgs<LensArgs> la{};
     gen_args(la);
     la.focus = gen->focus;
     std::memcpy(la.lens, gen->lens, (size_t)rv->samples * 2 * sizeof(double));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true>), dim3((unsigned)grid), dim3(64), lds,
-                       c->stream, la);
+    la.area = area;
+    if (area)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true, true>), dim3((unsigned)grid), dim3(64), lds,
+                         c->stream, la);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true>), dim3((unsigned)grid), dim3(64), lds,
+                         c->stream, static_cast<const LensArgs &>(la));
   });
 }
 
@@ -3859,6 +3922,7 @@ int rt_trace_radiance_resolve_async(rt_ctx *c, const rt_ray *rays, size_t n, int
                                     int depth, int fmt, void *out) {
   const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
+  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   if (n == 0) return RT_OK;
   if (misaligned(rays, out)) return RT_ERR_INVALID_ARG;
   const ResolveSpec rv{samples, weights};
@@ -3869,6 +3933,7 @@ int rt_trace_radiance_resolve(rt_ctx *c, const rt_ray *rays, size_t n, int sampl
                               int fmt, void *out, int on_device, rt_radiance_stats *st) {
   const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
+  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   Staged io[] = {{rays, &c->radiance.rays, n * (size_t)samples * sizeof(rt_ray), kStageIn},
                  {out, &c->radiance.out[0], n * radiance_record(fmt), kStageOut}};
   return staged_call(c, n, io, on_device, rt_radiance_stats_get, st, [&] {
@@ -3900,6 +3965,7 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   const Rows r = to_rows(rows, H);
   int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
   if (rc != RT_OK) return rc;
+  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   const long long row_rays = (long long)W * samples;  // one output row: the smallest chunk
   if (row_rays > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
   const size_t rec = radiance_record(fmt);
@@ -3960,6 +4026,7 @@ static int fused_validate(const rt_ctx *c, const rt_camera *cam, int W, int H, i
   real = 0;
   int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
   if (rc != RT_OK) return rc;
+  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   if ((long long)W * samples > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // rt_render_samples' row limit
   if ((long long)r.count * W > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // one launch: its pixels
   if (radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
@@ -4128,6 +4195,8 @@ __global__ __launch_bounds__(64) void add_counts_kernel(const unsigned long long
   acc[q] += s;
 }
 }  // namespace
+
+int rt_light_samples(const rt_ctx *c) { return c ? c->radiance.area_samples : 0; }
 
 int rt_add_counts(rt_ctx *c, unsigned long long *acc) {
   static_assert(kRtCountSlots == kCounters, "rt_stats' counters");

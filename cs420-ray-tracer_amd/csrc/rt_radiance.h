@@ -63,6 +63,18 @@ struct LensArgs : GenArgs {
 };
 static_assert(sizeof(LensArgs) <= 4096, "the kernel argument segment of a launch");
 
+// A resolving launch under area lights (rt_set_light_samples): any of the three argument blocks above
+// and, behind it, the context's table of shifted light records, [samples][q.nl] of them: record
+// s * q.nl + l is light l as sample s sees it.  The table lives in device memory -- 64 samples of 64
+// lights are 192 KiB, and even one [64][3] block more would push LensArgs past the argument segment --
+// and only its address travels here.  Appended, not a member of ResolveArgs: the blocks of the launches
+// without a table keep their layout, and so their kernels every operand offset.
+template <class Base>
+struct AreaArgs : Base {
+  const LightD *area;
+};
+static_assert(sizeof(AreaArgs<LensArgs>) <= 4096, "the kernel argument segment of a launch");
+
 template <bool kResolve, bool kGen, bool kLens>
 struct RadianceLaunch {
   using Args = RadianceArgs;
@@ -78,6 +90,14 @@ struct RadianceLaunch<true, true, false> {
 template <>
 struct RadianceLaunch<true, true, true> {
   using Args = LensArgs;
+};
+template <class Args, bool kArea>
+struct AreaLaunch {
+  using type = Args;
+};
+template <class Args>
+struct AreaLaunch<Args, true> {
+  using type = AreaArgs<Args>;
 };
 
 // path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
@@ -131,11 +151,23 @@ struct RadianceLaunch<true, true, true> {
 // pinhole ray meets, camera_lens_rays_kernel's arithmetic (rt_query.h).  The origin becomes a per-lane
 // value; the lens points and the focus distance are read wave-uniformly as the offsets are.  Only the ray
 // formation differs, and with kLens false none of it is emitted.
-template <bool kResolve, bool kGen = false, bool kLens = false>
+//
+// kArea (rt_set_light_samples, DESIGN.md section 5b, "Samples under area lights"): any resolving form
+// with sample s's light records read from row s of the context's table, ka.area + s * q.nl, instead of
+// q.lights.  The row is chosen once per sample, outside the level loop, so the whole chain of the sample
+// -- every level's to_light, dist, ldir, shadow ray and Phong terms -- sees one position per light.  s and
+// q.nl are wave-uniform, so the base is: the lane-per-ray loop's L stays a scalar load, the wide form's
+// helper lanes load lights[lh] per lane as before.  The records were formed on the host; the kernel adds
+// nothing.  The sweeps take a light anywhere: make_bound's margins are relative to its own P and the
+// lanes' distance from it, the walks' to the origin (in R, path_in_region) and to dist, and none to the
+// scene bound, so a row whose lights lie outside the uploaded bound changes no result and no counter
+// rule.  With kArea false none of it is emitted and the argument block is the form's own.
+template <bool kResolve, bool kGen = false, bool kLens = false, bool kArea = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(
-    const typename RadianceLaunch<kResolve, kGen, kLens>::Args ka) {
+    const typename AreaLaunch<typename RadianceLaunch<kResolve, kGen, kLens>::Args, kArea>::type ka) {
   static_assert(kResolve || !kGen, "the generating form resolves");
   static_assert(kGen || !kLens, "the lens form generates");
+  static_assert(kResolve || !kArea, "the light table is indexed by the sample");
   const RadianceArgs &a = reinterpret_cast<const RadianceArgs &>(ka);  // ResolveArgs::r, at offset 0
   const PathArgs &q = a.q;
   const int lane = (int)(threadIdx.x & 63);
@@ -182,6 +214,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
       o = mk(r0.x, r0.y, r1.x);
       d = normalized(mk(r1.y, r2.x, r2.y));  // Ray(o, d), ray.h:12: once
     }
+    const LightD *lights = q.lights;  // kArea: the sample's row of the table, for the whole of its chain
+    if constexpr (kArea) lights = ka.area + (size_t)s * (size_t)q.nl;
     bool alive = act;
     int key = -1;  // the sphere the ray leaves: groups the sweeps' lanes, changes no result
     int lev = 0;   // stack entries this lane holds
@@ -263,7 +297,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
           const int own = nth_set_bit(hm, r);  // the owner: the r-th hit lane
           const D3 hq = mk(__shfl(hp.x, own, 64), __shfl(hp.y, own, 64), __shfl(hp.z, own, 64));
           const int hq_i = RT_CK(kCkSphere, __shfl(hi, own, 64), q.n > 0 ? q.n : 1);
-          const LightD L = q.lights[lh];
+          const LightD L = lights[lh];
           const D3 lp = mk(L.px, L.py, L.pz);
           const D3 to_light = sub(lp, hq);
           const double dist = length(to_light);
@@ -286,7 +320,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
         }
       } else if (hm != 0) {
         for (int l = 0; l < q.nl; ++l) {
-          const LightD L = q.lights[l];
+          const LightD L = lights[l];
           const D3 lp = mk(L.px, L.py, L.pz);
           const D3 to_light = sub(lp, hp);
           const double dist = length(to_light);

@@ -23,6 +23,9 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   a pinhole only         include/camera.h:17-25          -> Renderer.camera_lens_rays, render_lens_samples[_async],
                                                             Group.render_lens_samples, lens_pattern (a thin lens:
                                                             depth of field for the multi-sample renders)
+  point lights only      include/scene.h:94-120          -> Renderer.set_light_samples, Group.set_light_samples,
+                                                            light_pattern (per-sample light positions: area
+                                                            lights, soft shadows, for the multi-sample renders)
 """
 from __future__ import annotations
 
@@ -253,6 +256,8 @@ SIGNATURES = {
                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
                                                C.POINTER(C.c_double), C.c_int, _P, C.c_int,
                                                C.POINTER(rt_radiance_stats)]),
+    "rt_set_light_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
+    "rt_group_set_light_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -452,6 +457,16 @@ class Renderer:
 
     def upload(self, scene: Scene):
         _check(self._L.rt_upload_scene(self._ctx, C.byref(scene.raw)), "rt_upload_scene", self._ctx, L=self._L)
+        self._num_lights = scene.num_lights
+
+    def set_light_samples(self, offsets):
+        """rt_set_light_samples: area lights for the multi-sample calls.  `offsets`: an [S][num_lights][3]
+        array-like (e.g. light_pattern(n, r, scene.num_lights)), the offset of light l for sample s, added to
+        its uploaded position; None clears the table.  While it is set, trace_radiance_resolve,
+        render_samples[_async] and render_lens_samples[_async] take S samples and shade sample s under the
+        moved lights; upload() clears it."""
+        tab, s = _light_table(offsets, getattr(self, "_num_lights", None))
+        _check(self._L.rt_set_light_samples(self._ctx, tab, s), "rt_set_light_samples", self._ctx, L=self._L)
 
     def render(self, cam: rt_camera, width: int, height: int, depth: int, rows: rt_rows | None = None,
                out=None, out_on_device: bool = False) -> tuple[object, rt_stats]:
@@ -780,6 +795,12 @@ class Group:
 
     def upload(self, scene: Scene):
         self._check_grp(self._L.rt_group_upload_scene(self._grp, C.byref(scene.raw)), "rt_group_upload_scene")
+        self._num_lights = scene.num_lights
+
+    def set_light_samples(self, offsets):
+        """rt_group_set_light_samples: Renderer.set_light_samples on every member."""
+        tab, s = _light_table(offsets, getattr(self, "_num_lights", None))
+        self._check_grp(self._L.rt_group_set_light_samples(self._grp, tab, s), "rt_group_set_light_samples")
 
     def set_antialias(self, samples: int):
         self._check_grp(self._L.rt_group_set_antialias(self._grp, samples), "rt_group_set_antialias")
@@ -911,6 +932,33 @@ def lens_pattern(n: int, aperture: float) -> list[tuple[float, float]]:
         v = (b + 0.5) / n * 2.0 - 1.0
         pts.append((u * math.sqrt(1.0 - v * v / 2.0) * aperture, v * math.sqrt(1.0 - u * u / 2.0) * aperture))
     return pts
+
+
+def light_pattern(n: int, radius: float, num_lights: int) -> list[list[tuple[float, float, float]]]:
+    """The n*n light offsets that go with grid_pattern(n), as set_light_samples takes them: sample s of
+    light l is point (s + 17*l) % (n*n) of lens_pattern(n, radius), a disk of radius `radius` (scene
+    units), laid in the horizontal plane as (x, 0, z).  The rotation by 17*l decorrelates the lights
+    from each other.  ray_hip --light-radius computes the same doubles."""
+    if num_lights < 0:
+        raise ValueError(f"light_pattern(num_lights={num_lights})")
+    disk = lens_pattern(n, radius)
+    return [[(disk[(s + 17 * l) % (n * n)][0], 0.0, disk[(s + 17 * l) % (n * n)][1]) for l in range(num_lights)]
+            for s in range(n * n)]
+
+
+def _light_table(offsets, num_lights):
+    """(the `light_xyz` argument, samples) of the light-table setters: `offsets` an [S][num_lights][3]
+    array-like, or None (the table is cleared).  num_lights: the uploaded scene's, None before an upload
+    (the call then reports the missing scene)."""
+    if offsets is None:
+        return None, 0
+    rows = [[tuple(float(x) for x in o) for o in row] for row in offsets]
+    nl = num_lights if num_lights is not None else (len(rows[0]) if rows else 0)
+    for row in rows:
+        if len(row) != nl or any(len(o) != 3 for o in row):
+            raise ValueError(f"light offsets are not [samples][{nl}][3]")
+    flat = [x for row in rows for o in row for x in o]
+    return (C.c_double * max(1, len(flat)))(*flat), len(rows)
 
 
 def _lens_points(lens, samples: int):

@@ -59,6 +59,11 @@
  *                                      a pinhole only, include/camera.h:17-25): rt_camera_sample_rays,
  *                                      rt_render_samples_async, rt_render_samples and rt_group_render_samples
  *                                      with each sample's ray leaving a point of a thin lens
+ *   rt_set_light_samples / rt_group_set_light_samples
+ *                                   <- (new) one rt_upload_scene with moved lights, one radiance call and a
+ *                                      reduction of the caller's per sample (the reference has point lights only,
+ *                                      include/scene.h:94-120): per-sample light positions for the multi-sample
+ *                                      entries, i.e. area lights with soft shadows
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -98,7 +103,9 @@ extern "C" {
                                    rt_trace_radiance_resolve_async, rt_render_samples) and their fused and
                                    group forms (rt_render_samples_async, rt_group_render_samples) and the
                                    thin-lens forms (rt_camera_lens_rays, rt_render_lens_samples_async,
-                                   rt_render_lens_samples, rt_group_render_lens_samples) */
+                                   rt_render_lens_samples, rt_group_render_lens_samples) and the light table
+                                   of the multi-sample entries (rt_set_light_samples,
+                                   rt_group_set_light_samples) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -670,6 +677,49 @@ int rt_render_lens_samples(rt_ctx *ctx, const rt_camera *cam, int width, int hei
                            const double *lens_xy, double focus, int samples, const double *weights /* nullable */,
                            int fb_format, void *out, int out_on_device, rt_radiance_stats *stats /* nullable */);
 
+/* ---- samples under area lights (soft shadows) -------------------------------
+   Replaces, per sample, one rt_upload_scene of the scene with its lights moved (a BVH and light-grid build
+   each), one rt_trace_radiance of that sample's rays with fp64 colours through memory, and the caller's own
+   reduction: a LIGHT TABLE, context state set once, which gives every sample of the multi-sample entries its
+   own light positions.
+   light_xyz: HOST memory, samples * num_lights * 3 doubles, num_lights the uploaded scene's; the offset of
+   light l for sample s is light_xyz[(s*num_lights + l)*3 .. +2], in scene units, ADDED to the uploaded
+   position.  NULL clears the table (samples is then ignored).  With a table, `samples` is its sample count.
+   Which launches read it: while a table is set, every RESOLVING radiance launch --
+   rt_trace_radiance_resolve[_async], rt_render_samples (through its resolve launches),
+   rt_render_samples_async, rt_render_lens_samples[_async], rt_group_render_samples and
+   rt_group_render_lens_samples.  For sample s (ray p*samples + s of pixel p) light l has the position
+     (fl(Lx + ox), fl(Ly + oy), fl(Lz + oz))       one fp64 add per component, no contraction
+   and its uploaded colour, for the WHOLE of that sample's chain: every reflection level, the shadow ray
+   (to_light, dist, ldir) and the Phong terms alike.  The records written are, bit for bit, what the same
+   call writes on a context whose scene was uploaded with those positions, sample by sample, resolved as the
+   call resolves.
+   What never reads it: rt_trace_radiance[_async] and the ray and path queries (no sample index), and every
+   render (rt_render*, the tile renders, rt_set_antialias, rt_group_render, rt_group_render_frames).  Without a
+   table every call writes exactly what it wrote before this entry existed.
+   Sample-count mismatch: a resolving call whose `samples` differs from the table's is RT_ERR_INVALID_ARG,
+   tested right behind the call's own samples range check, before any HIP call (also for n == 0 or no rows);
+   on a group rt_group_last_error names the two counts.
+   Any double is allowed: a non-finite offset gives that light a non-finite position and so a NaN direction
+   for that sample, handled as a light at the hit point is (rt_trace_paths above: not shadowed; its Phong
+   terms are what Scene::shade's arithmetic makes of a NaN, whose std::max(0.0, x) gives 0.0); it is never
+   an error.  A light moved outside the uploaded scene's bound costs speed at most: the sweeps' and walks'
+   margins are relative to the shadow ray's origin, the light and their distance, never to the bound.
+   rays_unaccelerated follows the uploaded scene's own query region (lights included), as before: it is the
+   one figure that may differ from a context whose scene was uploaded with the moved lights, whose region
+   follows them.
+   Synchronous: waits for the context's stream (work in flight may read the table being replaced, as
+   rt_upload_scene waits for the scene's), uploads samples * num_lights records of 48 bytes, and returns;
+   light_xyz is free on return.  The _async entries gain no launch, buffer or wait: they pass one pointer.
+   Lifetime: rt_upload_scene clears the table (the light count may change), rt_destroy frees it.  A scene
+   without lights accepts the call and stores an empty table: the launches write what they write without
+   one, and the sample-count check still holds.
+   Stats: unchanged rules -- rays_shadow = hits * lights per sample, the same counters and events, the
+   same 32-bit per-lane counter check of the fused launches.
+   Errors: NULL ctx, or a non-NULL light_xyz with samples outside 1..RT_MAX_SAMPLES, RT_ERR_INVALID_ARG
+   before any HIP call; no uploaded scene RT_ERR_NO_SCENE; an error leaves the previous table in force. */
+int rt_set_light_samples(rt_ctx *ctx, const double *light_xyz /* host, nullable */, int samples);
+
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
  * streams and shard buffers, ncclGather to device 0, rt_unpermute_rows -- with
@@ -742,6 +792,12 @@ int  rt_group_render_lens_samples(rt_group *grp, const rt_camera *cam, int width
                                   const double *offsets_xy, const double *lens_xy, double focus, int samples,
                                   const double *weights /* nullable */, int fb_format, void *out,
                                   int out_on_device, rt_radiance_stats *stats /* nullable */);
+
+/* rt_set_light_samples on every member ("samples under area lights" above): the two group sample renders
+   then shade sample s under the moved lights, byte for byte what the single-context calls write.
+   rt_group_upload_scene clears the table on every member.  Errors: rt_set_light_samples', with the cause
+   in rt_group_last_error; RT_ERR_NO_SCENE without rt_group_upload_scene. */
+int  rt_group_set_light_samples(rt_group *grp, const double *light_xyz /* host, nullable */, int samples);
 
 #ifdef __cplusplus
 }
