@@ -41,6 +41,10 @@
 // light_pattern(N, R, num_lights)[s][l] of rt_hip.py (a horizontal disk of radius
 // R), set once through rt_set_light_samples, or rt_group_set_light_samples, ahead
 // of the render.  Without --light-radius nothing changes.
+// --gloss SCALE [--gloss-bounces B] (only with --supersample N; B in 1..RT_MAX_GLOSS_BOUNCES, default 1;
+// with or without --aperture, --light-radius and --sample-devices): glossy reflections.  The scene
+// file's roughness column times SCALE, and gloss_pattern(N, B) of rt_hip.py, set once through
+// rt_set_gloss_samples, or rt_group_set_gloss_samples, ahead of the render.  Without --gloss nothing changes.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -78,14 +82,18 @@ struct Opts {
   double aperture = 0.0, focus = 0.0;
   bool area = false;  // --light-radius R: --supersample under rt_set_light_samples
   double light_radius = 0.0;
+  bool gloss = false;  // --gloss SCALE [--gloss-bounces B]: --supersample under rt_set_gloss_samples
+  bool gloss_bounces_given = false;
+  double gloss_scale = 0.0;
+  int gloss_bounces = 1;
 };
 
 int usage(const char *argv0) {
   std::fprintf(stderr,
                "usage: %s [--openmp] [-a | --supersample N] [--width W] [--height H] [--depth D] [--gpus G] [--device N]\n"
                "          [--devices D0,D1,... [--frames N [--batch B]]] [--out FILE] [--p6] [--repeat N]\n"
-               "          [--sample-devices D0,D1,...] [--aperture R [--focus F]] [--light-radius R] [--json]\n"
-               "          [scene.txt]\n"
+               "          [--sample-devices D0,D1,...] [--aperture R [--focus F]] [--light-radius R]\n"
+               "          [--gloss SCALE [--gloss-bounces B]] [--json] [scene.txt]\n"
                "  --devices LIST  one row shard per listed device through the library's device group\n"
                "                  (a device may repeat: 0,0,0); not with --gpus > 1 or --force-gather\n"
                "  --frames N      with --devices: each pass renders N >= 1 frames of the view as one pipelined\n"
@@ -97,8 +105,11 @@ int usage(const char *argv0) {
                "  --aperture R    with --supersample: depth of field, a thin lens of radius R >= 0 (scene units);\n"
                "                  --focus F: the distance of the sharp plane (default: camera to look-at point)\n"
                "  --light-radius R  with --supersample: area lights, each light a horizontal disk of radius R >= 0\n"
-               "                  (scene units) sampled once per pixel sample: soft shadows\n",
-               argv0, RT_MAX_FRAMES, RT_MAX_FRAMES);
+               "                  (scene units) sampled once per pixel sample: soft shadows\n"
+               "  --gloss SCALE   with --supersample: glossy reflections, the scene file's roughness column times\n"
+               "                  SCALE bending each sample's reflection rays; --gloss-bounces B: the reflection\n"
+               "                  levels bent, 1..%d (default 1), the later ones stay mirrors\n",
+               argv0, RT_MAX_FRAMES, RT_MAX_FRAMES, RT_MAX_GLOSS_BOUNCES);
   return 2;
 }
 
@@ -160,7 +171,8 @@ int render_single(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8
 // with --sample-devices through rt_group_render_samples on a group of band 8.  With --aperture R the
 // lens forms of the two calls, sample s at the lens point of grid cell N*N-1-s (rt_hip.py lens_pattern:
 // the same doubles in the same order).  With --light-radius R the light table of rt_hip.py
-// light_pattern(N, R, num_lights), restated the same way, is set ahead of the render.
+// light_pattern(N, R, num_lights), restated the same way, is set ahead of the render; with --gloss SCALE
+// the gloss table of gloss_pattern(N, B) and the scene file's roughness column times SCALE.
 int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam, uint8_t *img, Result &res) {
   const int N = o.supersample;
   std::vector<double> offsets;
@@ -196,6 +208,28 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
       }
     if (light_xyz.empty()) light_xyz.push_back(0.0);  // a scene without lights: a non-NULL, empty table
   }
+  std::vector<double> gloss_xyz, rough;  // [s][b]: disk point i = (s + 17 (b+1)) % (N*N) lifted into the unit ball
+  if (o.gloss) {
+    const int nn = N * N;
+    for (int s = 0; s < nn; s++)
+      for (int b = 0; b < o.gloss_bounces; b++) {
+        const int i = (s + 17 * (b + 1)) % nn;
+        double x, y;
+        disk_point(i, 1.0, x, y);
+        const double h = (double)(2 * ((7 * i + 3) % nn) + 1) / nn - 1.0;
+        gloss_xyz.push_back(x);
+        gloss_xyz.push_back(y);
+        gloss_xyz.push_back(h * std::sqrt(std::max(0.0, 1.0 - x * x - y * y)));
+      }
+    int n = 0;
+    rough.resize((size_t)sc.num_spheres + 1);
+    CK(rt_scene_load_roughness(o.scene.c_str(), rough.data(), sc.num_spheres, &n));
+    if (n != sc.num_spheres) {
+      std::fprintf(stderr, "%s changed while it was read\n", o.scene.c_str());
+      return 1;
+    }
+    for (double &r : rough) r = r * o.gloss_scale;
+  }
   double focus = o.focus;
   if (o.lens && !o.focus_given) {
     const double dx = sc.cam_look_at[0] - sc.cam_position[0], dy = sc.cam_look_at[1] - sc.cam_position[1],
@@ -215,6 +249,8 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
     CK(rt_group_create(o.sample_devices.data(), (int)o.sample_devices.size(), 8, &grp));
     int rc = rt_group_upload_scene(grp, &sc);
     if (rc == RT_OK && o.area) rc = rt_group_set_light_samples(grp, light_xyz.data(), N * N);
+    if (rc == RT_OK && o.gloss)
+      rc = rt_group_set_gloss_samples(grp, rough.data(), gloss_xyz.data(), N * N, o.gloss_bounces);
     for (int it = 0; it < o.repeat && rc == RT_OK; it++) {
       auto t0 = std::chrono::high_resolution_clock::now();
       rc = o.lens ? rt_group_render_lens_samples(grp, &cam, o.width, o.height, o.depth, offsets.data(), lens.data(),
@@ -234,6 +270,7 @@ int render_supersampled(const Opts &o, const rt_scene &sc, const rt_camera &cam,
   CK(rt_create(o.device, &ctx));
   CK(rt_upload_scene(ctx, &sc));
   if (o.area) CK(rt_set_light_samples(ctx, light_xyz.data(), N * N));
+  if (o.gloss) CK(rt_set_gloss_samples(ctx, rough.data(), gloss_xyz.data(), N * N, o.gloss_bounces));
   for (int it = 0; it < o.repeat; it++) {
     auto t0 = std::chrono::high_resolution_clock::now();
     if (o.lens)
@@ -482,6 +519,8 @@ int main(int argc, char **argv) {
     else if (a == "--sample-devices") { if (i + 1 >= argc || !parse_devices(argv[++i], o.sample_devices)) return usage(argv[0]); }
     else if (a == "--aperture") { if (!next_double(o.aperture) || !(o.aperture >= 0.0)) return usage(argv[0]); o.lens = true; }
     else if (a == "--light-radius") { if (!next_double(o.light_radius) || !(o.light_radius >= 0.0)) return usage(argv[0]); o.area = true; }
+    else if (a == "--gloss") { if (!next_double(o.gloss_scale)) return usage(argv[0]); o.gloss = true; }
+    else if (a == "--gloss-bounces") { if (!next(o.gloss_bounces) || o.gloss_bounces < 1 || o.gloss_bounces > RT_MAX_GLOSS_BOUNCES) return usage(argv[0]); o.gloss_bounces_given = true; }
     else if (a == "--focus") { if (!next_double(o.focus)) return usage(argv[0]); o.focus_given = true; }
     else if (a == "--json") o.json = true;
     else if (a == "-h" || a == "--help") return usage(argv[0]);
@@ -493,6 +532,7 @@ int main(int argc, char **argv) {
   if (!o.sample_devices.empty() && !o.supersample) return usage(argv[0]);  // with --supersample: the line above
   if ((o.lens && !o.supersample) || (o.focus_given && !o.lens)) return usage(argv[0]);
   if (o.area && !o.supersample) return usage(argv[0]);
+  if ((o.gloss && !o.supersample) || (o.gloss_bounces_given && !o.gloss)) return usage(argv[0]);
   if ((o.frames > 0 && o.devices.empty()) || (o.batch >= 0 && o.frames < 0)) return usage(argv[0]);
 
   std::printf("Testing scene loader with: %s\n\n", o.scene.c_str());  // main.cpp:116

@@ -584,6 +584,32 @@ int rt_group_set_light_samples(rt_group *g, const double *light_xyz, int samples
   return RT_OK;
 }
 
+int rt_group_set_gloss_samples(rt_group *g, const double *roughness, const double *gloss_xyz, int samples,
+                               int bounces) {
+  if (!g) return RT_ERR_INVALID_ARG;
+  if (gloss_xyz && !roughness) {
+    g->err = "rt_group_set_gloss_samples: a table without the spheres' roughness";
+    return RT_ERR_INVALID_ARG;
+  }
+  if (gloss_xyz && (samples < 1 || samples > RT_MAX_SAMPLES)) {
+    g->err = "rt_group_set_gloss_samples: samples outside 1..RT_MAX_SAMPLES";
+    return RT_ERR_INVALID_ARG;
+  }
+  if (gloss_xyz && (bounces < 1 || bounces > RT_MAX_GLOSS_BOUNCES)) {
+    g->err = "rt_group_set_gloss_samples: bounces outside 1..RT_MAX_GLOSS_BOUNCES";
+    return RT_ERR_INVALID_ARG;
+  }
+  if (!g->has_scene) {
+    g->err = "rt_group_set_gloss_samples: no scene uploaded";
+    return RT_ERR_NO_SCENE;
+  }
+  for (int i = 0; i < (int)g->m.size(); i++) {
+    const int rc = rt_set_gloss_samples(g->m[i].ctx, roughness, gloss_xyz, samples, bounces);
+    if (rc != RT_OK) return member_fail(g, i, rc, "rt_set_gloss_samples");
+  }
+  return RT_OK;
+}
+
 int rt_group_set_antialias(rt_group *g, int samples) {
   if (!g || (samples != 1 && samples != 4)) return RT_ERR_INVALID_ARG;
   for (int i = 0; i < (int)g->m.size(); i++) {
@@ -629,6 +655,12 @@ static int group_render_samples(rt_group *g, const char *name, const rt_camera *
     if (table != 0 && table != samples) {
       g->err = std::string(name) + ": samples (" + std::to_string(samples) + ") differs from the light table's (" +
                std::to_string(table) + ", rt_group_set_light_samples)";
+      return RT_ERR_INVALID_ARG;
+    }
+    const int gloss = rt_gloss_samples(mb.ctx);  // likewise (rt_group_set_gloss_samples)
+    if (gloss != 0 && gloss != samples) {
+      g->err = std::string(name) + ": samples (" + std::to_string(samples) + ") differs from the gloss table's (" +
+               std::to_string(gloss) + ", rt_group_set_gloss_samples)";
       return RT_ERR_INVALID_ARG;
     }
   }

@@ -43,7 +43,8 @@ void set3(double *d, double x, double y, double z) {
   d[2] = z;
 }
 
-int parse_stream(std::istream &in, rt_scene *out, int verbose) {
+// rough: where given, column 9 of every accepted sphere record, in file order (rt_scene_parse_roughness).
+int parse_stream(std::istream &in, rt_scene *out, int verbose, std::vector<double> *rough = nullptr) {
   std::memset(out, 0, sizeof(*out));
   set3(out->cam_look_at, 0, 0, -1);  // CameraConfig() defaults, scene.h:22
   out->cam_fov = 60.0;
@@ -75,9 +76,10 @@ int parse_stream(std::istream &in, rt_scene *out, int verbose) {
       set3(s.center, v[0], v[1], v[2]);
       s.radius = v[3];
       set3(s.color, v[4], v[5], v[6]);
-      s.reflectivity = v[7];  // "metallic"; v[8] (roughness) is dropped as upstream
+      s.reflectivity = v[7];  // "metallic"; v[8] (roughness) is dropped as upstream: rt_sphere has no field for it
       s.shininess = v[9];
       g.spheres.push_back(s);
+      if (rough) rough->push_back(v[8]);
     } else if (type == "light") {
       if (!read(7)) { warn("light"); continue; }
       rt_light l;
@@ -122,6 +124,19 @@ V normalized(V a) {
   return {a.x / len, a.y / len, a.z / len};
 }
 void put(double *d, V v) { set3(d, v.x, v.y, v.z); }
+
+// The roughness column through parse_stream itself, so that index i is scene.spheres[i] by construction;
+// the scene it builds on the way is dropped.
+int roughness_of(std::istream &in, double *out, int capacity, int *n_out) {
+  rt_scene sc;
+  std::vector<double> rough;
+  const int rc = parse_stream(in, &sc, 0, &rough);
+  rt_scene_free(&sc);
+  if (rc != RT_OK) return rc;
+  for (size_t i = 0; i < rough.size() && i < (size_t)capacity; i++) out[i] = rough[i];
+  *n_out = (int)rough.size();
+  return RT_OK;
+}
 
 }  // namespace
 
@@ -168,6 +183,19 @@ int rt_scene_load(const char *path, rt_scene *out, int verbose) {
     return RT_ERR_IO;
   }
   return parse_stream(f, out, verbose);
+}
+
+int rt_scene_parse_roughness(const char *text, double *out, int capacity, int *n_out) {
+  if (!text || !n_out || capacity < 0 || (!out && capacity > 0)) return RT_ERR_INVALID_ARG;
+  std::istringstream in{std::string(text)};
+  return roughness_of(in, out, capacity, n_out);
+}
+
+int rt_scene_load_roughness(const char *path, double *out, int capacity, int *n_out) {
+  if (!path || !n_out || capacity < 0 || (!out && capacity > 0)) return RT_ERR_INVALID_ARG;
+  std::ifstream f(path);
+  if (!f.is_open()) return RT_ERR_IO;
+  return roughness_of(f, out, capacity, n_out);
 }
 
 void rt_scene_free(rt_scene *scene) {

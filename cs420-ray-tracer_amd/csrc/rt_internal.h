@@ -25,5 +25,7 @@ RT_INTERNAL int rt_launch_ms(rt_ctx *ctx, long long index, double *ms);
 
 // The sample count of the context's light table (rt_set_light_samples); 0 without one.  No HIP call.
 RT_INTERNAL int rt_light_samples(const rt_ctx *ctx);
+// The same of its gloss table (rt_set_gloss_samples).
+RT_INTERNAL int rt_gloss_samples(const rt_ctx *ctx);
 
 #endif  // RT_INTERNAL_H

@@ -1836,6 +1836,12 @@ struct TraceState {
   // the stream idle (the setter, rt_upload_scene).
   DevBuf<LightD> area;
   int area_samples = 0;
+  // radiance only: the gloss table of the resolving launches (rt_set_gloss_samples), [gloss_samples]
+  // [gloss_bounces] points, and the scene's spheres' roughness; gloss_samples == 0: no table.  Replaced or
+  // cleared as the light table is.
+  DevBuf<D3> gloss;
+  DevBuf<double> rough;
+  int gloss_samples = 0, gloss_bounces = 0;
 };
 
 struct rt_ctx {
@@ -3373,6 +3379,9 @@ int rt_upload_scene(rt_ctx *c, const rt_scene *s) {
   free_scene(c);
   c->radiance.area.reset();  // the light table goes with the scene: the light count may change
   c->radiance.area_samples = 0;
+  c->radiance.gloss.reset();  // and the gloss table: the sphere count may change
+  c->radiance.rough.reset();
+  c->radiance.gloss_samples = c->radiance.gloss_bounces = 0;
   const bool big = s->num_spheres > kBvhAlwaysAbove;
   // leaves of 2 spheres (+0.6..0.9 % over 4 on synth200 with the merged levels);
   // 1 above kBvhAlwaysAbove, where every closest hit walks (synth10k 4.37 -> 4.16 ms)
@@ -3711,6 +3720,41 @@ static bool light_table_mismatch(const rt_ctx *c, int samples) {
   return c->radiance.area_samples != 0 && c->radiance.area_samples != samples;
 }
 
+// The gloss table of the resolving launches: the caller's points and the spheres' roughness, uploaded as
+// they are; the kernel forms rd + g * roughness itself (radiance_kernel, kGloss).
+int rt_set_gloss_samples(rt_ctx *c, const double *roughness, const double *xyz, int samples, int bounces) {
+  if (!c) return RT_ERR_INVALID_ARG;
+  if (xyz && (!roughness || samples < 1 || samples > RT_MAX_SAMPLES || bounces < 1 || bounces > RT_MAX_GLOSS_BOUNCES))
+    return RT_ERR_INVALID_ARG;
+  if (!c->scene.has_scene) return RT_ERR_NO_SCENE;
+  RT_TRY(c, hipSetDevice(c->device));
+  RT_TRY(c, hipStreamSynchronize(c->stream));  // work in flight may read the table being replaced
+  TraceState &rs = c->radiance;
+  if (!xyz) {
+    rs.gloss.reset();
+    rs.rough.reset();
+    rs.gloss_samples = rs.gloss_bounces = 0;
+    return RT_OK;
+  }
+  const size_t np = (size_t)samples * (size_t)bounces;
+  std::vector<D3> pts(np);
+  for (size_t i = 0; i < np; i++) pts[i] = D3{xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]};
+  const std::vector<double> rough(roughness, roughness + c->scene.nsph);
+  DevBuf<D3> next;  // the previous table stays in force if this fails
+  DevBuf<double> next_rough;
+  RT_TRY(c, next.upload(pts, 1));
+  RT_TRY(c, next_rough.upload(rough, 1));
+  rs.gloss = std::move(next);
+  rs.rough = std::move(next_rough);
+  rs.gloss_samples = samples, rs.gloss_bounces = bounces;
+  return RT_OK;
+}
+
+// `samples` of a resolving call against the gloss table's, where a table is set: they agree.
+static bool gloss_table_mismatch(const rt_ctx *c, int samples) {
+  return c->radiance.gloss_samples != 0 && c->radiance.gloss_samples != samples;
+}
+
 // The most reflection-stack scratch a radiance launch takes.  A launch of
 // `grid` one-wave workgroups at `depth` needs grid * 64 * (depth - 1) entries
 // of 32 bytes: 32 MiB per level below the first for the full grid of 64 waves
@@ -3749,11 +3793,52 @@ static long long radiance_grid(const rt_ctx *c, size_t n, int depth) {
   return grid;
 }
 
+// The tables of a context that a resolving launch reads: each nullptr where none is set (or the scene has
+// nothing for it to act on: no lights, no spheres).
+struct ResolveTables {
+  const LightD *area;
+  const D3 *gloss;
+  const double *rough;
+  int bounces;
+};
+
+// A resolving launch of the form <kGen, kLens> on its own argument block: the instantiation the tables
+// choose (kArea, kGloss), the block followed by their addresses.
+extern "C++" {
+template <bool kGen, bool kLens, class Base>
+static void resolve_go(const Base &b, const ResolveTables &t, unsigned grid, size_t lds, hipStream_t stream) {
+  auto go = [&](auto kernel, const auto &args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, stream, args);
+  };
+  auto with_gloss = [&](auto &x) { x.gloss = t.gloss, x.rough = t.rough, x.bounces = t.bounces; };
+  if (!t.area && !t.gloss) {
+    go(radiance_kernel<true, kGen, kLens>, b);
+  } else if (!t.gloss) {
+    AreaArgs<Base> x{};
+    static_cast<Base &>(x) = b;
+    x.area = t.area;
+    go(radiance_kernel<true, kGen, kLens, true>, x);
+  } else if (!t.area) {
+    GlossArgs<Base> x{};
+    static_cast<Base &>(x) = b;
+    with_gloss(x);
+    go(radiance_kernel<true, kGen, kLens, false, true>, x);
+  } else {
+    GlossArgs<AreaArgs<Base>> x{};
+    static_cast<Base &>(x) = b;
+    x.area = t.area;
+    with_gloss(x);
+    go(radiance_kernel<true, kGen, kLens, true, true>, x);
+  }
+}
+}  // extern "C++"
+
 // One radiance launch, validated by its entry point: n records from n rays (rv == nullptr,
 // radiance_kernel<false>), from n * rv->samples rays (radiance_kernel<true>) or, with `gen`, from
 // n * rv->samples rays the lanes form themselves (radiance_kernel<true, true>, or with gen->lens
 // radiance_kernel<true, true, true>; rays == nullptr).  A resolving launch of a context with a light table
-// (and lights) is the same form's kArea instantiation, its argument block followed by the table's address.
+// (and lights) is the same form's kArea instantiation, its argument block followed by the table's address;
+// of one with a gloss table (and spheres) the kGloss instantiation, likewise (resolve_go).
 static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, int fmt, void *out,
                            const ResolveSpec *rv, const GenSpec *gen = nullptr) {
   int rc;
@@ -3787,17 +3872,13 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       for (int s = 0; s < rv->samples; s++) ra.w[s] = rv->weights ? rv->weights[s] : 1.0;
     };
     lds += 64 * sizeof(D3);  // the wave's accumulators, right behind its parked colours
-    const LightD *area = rs.area_samples != 0 && c->scene.nlight > 0 ? rs.area.get() : nullptr;
+    const ResolveTables tab{rs.area_samples != 0 && c->scene.nlight > 0 ? rs.area.get() : nullptr,
+                            rs.gloss_samples != 0 && c->scene.nsph > 0 ? rs.gloss.get() : nullptr, rs.rough.get(),
+                            rs.gloss_bounces};
     if (!gen) {
-      AreaArgs<ResolveArgs> ra{};
+      ResolveArgs ra{};
       resolve_args(ra);
-      ra.area = area;
-      if (area)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, false, false, true>), dim3((unsigned)grid), dim3(64),
-                           lds, c->stream, ra);
-      else
-        hipLaunchKernelGGL(radiance_kernel<true>, dim3((unsigned)grid), dim3(64), lds, c->stream,
-                           static_cast<const ResolveArgs &>(ra));
+      resolve_go<false, false>(ra, tab, (unsigned)grid, lds, c->stream);
       return;
     }
     auto gen_args = [&](GenArgs &ga) {
@@ -3807,28 +3888,16 @@ static int radiance_launch(rt_ctx *c, const rt_ray *rays, size_t n, int depth, i
       std::memcpy(ga.xy, gen->offsets, (size_t)rv->samples * 2 * sizeof(double));  // by value: free on return
     };
     if (!gen->lens) {
-      AreaArgs<GenArgs> ga{};
+      GenArgs ga{};
       gen_args(ga);
-      ga.area = area;
-      if (area)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, false, true>), dim3((unsigned)grid), dim3(64),
-                           lds, c->stream, ga);
-      else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true>), dim3((unsigned)grid), dim3(64), lds,
-                           c->stream, static_cast<const GenArgs &>(ga));
+      resolve_go<true, false>(ga, tab, (unsigned)grid, lds, c->stream);
       return;
     }
-    AreaArgs<LensArgs> la{};
+    LensArgs la{};
     gen_args(la);
     la.focus = gen->focus;
     std::memcpy(la.lens, gen->lens, (size_t)rv->samples * 2 * sizeof(double));
-    la.area = area;
-    if (area)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true, true>), dim3((unsigned)grid), dim3(64), lds,
-                         c->stream, la);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(radiance_kernel<true, true, true>), dim3((unsigned)grid), dim3(64), lds,
-                         c->stream, static_cast<const LensArgs &>(la));
+    resolve_go<true, true>(la, tab, (unsigned)grid, lds, c->stream);
   });
 }
 
@@ -3922,7 +3991,7 @@ int rt_trace_radiance_resolve_async(rt_ctx *c, const rt_ray *rays, size_t n, int
                                     int depth, int fmt, void *out) {
   const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
-  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
+  if (light_table_mismatch(c, samples) || gloss_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   if (n == 0) return RT_OK;
   if (misaligned(rays, out)) return RT_ERR_INVALID_ARG;
   const ResolveSpec rv{samples, weights};
@@ -3933,7 +4002,7 @@ int rt_trace_radiance_resolve(rt_ctx *c, const rt_ray *rays, size_t n, int sampl
                               int fmt, void *out, int on_device, rt_radiance_stats *st) {
   const int rc = radiance_validate(c, rays, n, samples, depth, fmt, out);
   if (rc != RT_OK) return rc;
-  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
+  if (light_table_mismatch(c, samples) || gloss_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   Staged io[] = {{rays, &c->radiance.rays, n * (size_t)samples * sizeof(rt_ray), kStageIn},
                  {out, &c->radiance.out[0], n * radiance_record(fmt), kStageOut}};
   return staged_call(c, n, io, on_device, rt_radiance_stats_get, st, [&] {
@@ -3965,7 +4034,7 @@ int rt_render_samples(rt_ctx *c, const rt_camera *cam, int W, int H, int depth, 
   const Rows r = to_rows(rows, H);
   int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
   if (rc != RT_OK) return rc;
-  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
+  if (light_table_mismatch(c, samples) || gloss_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   const long long row_rays = (long long)W * samples;  // one output row: the smallest chunk
   if (row_rays > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;
   const size_t rec = radiance_record(fmt);
@@ -4026,7 +4095,7 @@ static int fused_validate(const rt_ctx *c, const rt_camera *cam, int W, int H, i
   real = 0;
   int rc = sample_rays_validate(c, cam, W, H, r, offsets, samples);
   if (rc != RT_OK) return rc;
-  if (light_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
+  if (light_table_mismatch(c, samples) || gloss_table_mismatch(c, samples)) return RT_ERR_INVALID_ARG;
   if ((long long)W * samples > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // rt_render_samples' row limit
   if ((long long)r.count * W > (long long)INT32_MAX) return RT_ERR_INVALID_ARG;  // one launch: its pixels
   if (radiance_record(fmt) == 0) return RT_ERR_INVALID_ARG;
@@ -4197,6 +4266,7 @@ __global__ __launch_bounds__(64) void add_counts_kernel(const unsigned long long
 }  // namespace
 
 int rt_light_samples(const rt_ctx *c) { return c ? c->radiance.area_samples : 0; }
+int rt_gloss_samples(const rt_ctx *c) { return c ? c->radiance.gloss_samples : 0; }
 
 int rt_add_counts(rt_ctx *c, unsigned long long *acc) {
   static_assert(kRtCountSlots == kCounters, "rt_stats' counters");

@@ -75,6 +75,20 @@ struct AreaArgs : Base {
 };
 static_assert(sizeof(AreaArgs<LensArgs>) <= 4096, "the kernel argument segment of a launch");
 
+// A resolving launch with glossy reflections (rt_set_gloss_samples): any of the blocks above, AreaArgs among
+// them, and behind it the context's gloss table, [samples][bounces] points g, and the spheres' roughness:
+// sample s's reflection ray off sphere i at level k < bounces leaves along rd + g[s * bounces + k] *
+// rough[i] where that stays on rd's side of the surface.  Both live in device memory (64 samples of 63
+// bounces are 94.5 KiB) and only their addresses travel here, appended for AreaArgs' reason: the blocks of
+// the launches without a table keep their layout.
+template <class Base>
+struct GlossArgs : Base {
+  const D3 *gloss;
+  const double *rough;
+  int bounces;
+};
+static_assert(sizeof(GlossArgs<AreaArgs<LensArgs>>) <= 4096, "the kernel argument segment of a launch");
+
 template <bool kResolve, bool kGen, bool kLens>
 struct RadianceLaunch {
   using Args = RadianceArgs;
@@ -98,6 +112,14 @@ struct AreaLaunch {
 template <class Args>
 struct AreaLaunch<Args, true> {
   using type = AreaArgs<Args>;
+};
+template <class Args, bool kGloss>
+struct GlossLaunch {
+  using type = Args;
+};
+template <class Args>
+struct GlossLaunch<Args, true> {
+  using type = GlossArgs<Args>;
 };
 
 // path_kernel's shape: one wave per workgroup, one ray per lane, grid-stride
@@ -162,12 +184,24 @@ struct AreaLaunch<Args, true> {
 // lanes' distance from it, the walks' to the origin (in R, path_in_region) and to dist, and none to the
 // scene bound, so a row whose lights lie outside the uploaded bound changes no result and no counter
 // rule.  With kArea false none of it is emitted and the argument block is the form's own.
-template <bool kResolve, bool kGen = false, bool kLens = false, bool kArea = false>
+//
+// kGloss (rt_set_gloss_samples, DESIGN.md section 5b, "Samples with glossy reflections"): any resolving
+// form, with or without kArea, whose reflection ray off sphere hi at level k < ka.bounces is bent: the
+// mirror direction rd plus sample s's point of the table for that level, scaled by the sphere's roughness,
+// where the sum stays on rd's side of the surface (the signs of the two dot products with the normal agree
+// and neither is zero or a NaN); otherwise, and for roughness 0 and every level from ka.bounces on, rd as
+// before.  s, k and ka.bounces are wave-uniform: the level test is a scalar branch and the point a scalar
+// load; the roughness is loaded per lane by the lanes that spawn (hi is a sphere only for a hit, and the
+// array is empty for a scene without spheres).  The spawn decision, the origin, the stack and every
+// counter are untouched.  With kGloss false none of it is emitted and the argument block is the form's own.
+template <bool kResolve, bool kGen = false, bool kLens = false, bool kArea = false, bool kGloss = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void radiance_kernel(
-    const typename AreaLaunch<typename RadianceLaunch<kResolve, kGen, kLens>::Args, kArea>::type ka) {
+    const typename GlossLaunch<
+        typename AreaLaunch<typename RadianceLaunch<kResolve, kGen, kLens>::Args, kArea>::type, kGloss>::type ka) {
   static_assert(kResolve || !kGen, "the generating form resolves");
   static_assert(kGen || !kLens, "the lens form generates");
   static_assert(kResolve || !kArea, "the light table is indexed by the sample");
+  static_assert(kResolve || !kGloss, "the gloss table is indexed by the sample");
   const RadianceArgs &a = reinterpret_cast<const RadianceArgs &>(ka);  // ResolveArgs::r, at offset 0
   const PathArgs &q = a.q;
   const int lane = (int)(threadIdx.x & 63);
@@ -354,7 +388,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ra
       // by the lanes that spawn one (the others' chains have ended)
       const D3 rd = sub(d, scale(scale(nrm, 2.0), dot(d, nrm)));
       o = add(hp, scale(nrm, kEps));
-      d = renormalized(rd);
+      if constexpr (kGloss) {
+        D3 chosen = rd;
+        if (k < ka.bounces) {  // wave-uniform; beyond the table every bounce is a mirror
+          // read through the constant address space: the table is read-only for the whole launch and the
+          // address is wave-uniform, which makes the point two scalar loads (a plain load stays a vector one,
+          // the stack's stores ahead of it in the loop keep the compiler from proving the table invariant)
+          typedef const __attribute__((address_space(4))) double *ConstDoubles;
+          const ConstDoubles gp = (ConstDoubles)(ka.gloss + ((size_t)s * (size_t)ka.bounces + (size_t)k));
+          const D3 g = mk(gp[0], gp[1], gp[2]);
+          const double rough = spawn ? ka.rough[hi] : 0.0;
+          const D3 rp = add(rd, scale(g, rough));  // the product rounded, then the sum
+          // refused on the wrong side of the surface, in the tangent plane, and for a NaN
+          if (rough != 0.0 && dot(rp, nrm) * dot(rd, nrm) > 0.0) chosen = rp;
+        }
+        d = renormalized(chosen);
+      } else {
+        d = renormalized(rd);
+      }
       key = spawn ? hi : key;
       alive = spawn;
     }

@@ -26,6 +26,10 @@ Reference interfaces mirrored (file:line in shininglegend/cs420-ray-tracer):
   point lights only      include/scene.h:94-120          -> Renderer.set_light_samples, Group.set_light_samples,
                                                             light_pattern (per-sample light positions: area
                                                             lights, soft shadows, for the multi-sample renders)
+  a perfect mirror       src/main.cpp:45-48              -> Renderer.set_gloss_samples, Group.set_gloss_samples,
+                                                            gloss_pattern, scene_roughness (the scene files'
+                                                            roughness column, which scene_loader.h:66-70 drops:
+                                                            glossy reflections for the multi-sample renders)
 """
 from __future__ import annotations
 
@@ -43,6 +47,7 @@ VARIANTS = {"tuning": os.path.join(HERE, "variants", "librt_hip_tuning.so"),
             "check": os.path.join(HERE, "variants", "librt_hip_check.so")}
 
 RT_MAX_DEPTH = 64
+RT_MAX_GLOSS_BOUNCES = RT_MAX_DEPTH - 1
 ABI_VERSION = 12  # RT_HIP_ABI_VERSION in include/rt_hip.h
 MAX_FRAMES = 32  # RT_MAX_FRAMES
 
@@ -258,6 +263,10 @@ SIGNATURES = {
                                                C.POINTER(rt_radiance_stats)]),
     "rt_set_light_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "rt_group_set_light_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
+    "rt_set_gloss_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int]),
+    "rt_group_set_gloss_samples": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int]),
+    "rt_scene_parse_roughness": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
+    "rt_scene_load_roughness": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
     "rt_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(_P)]),
     "rt_group_destroy": (None, [_P]),
     "rt_group_size": (C.c_int, [_P]),
@@ -458,6 +467,17 @@ class Renderer:
     def upload(self, scene: Scene):
         _check(self._L.rt_upload_scene(self._ctx, C.byref(scene.raw)), "rt_upload_scene", self._ctx, L=self._L)
         self._num_lights = scene.num_lights
+        self._num_spheres = scene.num_spheres
+
+    def set_gloss_samples(self, roughness, table):
+        """rt_set_gloss_samples: glossy reflections for the multi-sample calls.  `roughness`: num_spheres
+        doubles (e.g. scene_roughness(path)); `table`: an [S][B][3] array-like (e.g. gloss_pattern(n, B)), the
+        point that bends sample s's reflection ray at bounce b, scaled by the roughness of the sphere it
+        leaves; None clears the table.  While it is set, trace_radiance_resolve, render_samples[_async] and
+        render_lens_samples[_async] take S samples; upload() clears it."""
+        rough, tab, s, b = _gloss_table(roughness, table, getattr(self, "_num_spheres", None))
+        _check(self._L.rt_set_gloss_samples(self._ctx, rough, tab, s, b), "rt_set_gloss_samples", self._ctx,
+               L=self._L)
 
     def set_light_samples(self, offsets):
         """rt_set_light_samples: area lights for the multi-sample calls.  `offsets`: an [S][num_lights][3]
@@ -796,6 +816,12 @@ class Group:
     def upload(self, scene: Scene):
         self._check_grp(self._L.rt_group_upload_scene(self._grp, C.byref(scene.raw)), "rt_group_upload_scene")
         self._num_lights = scene.num_lights
+        self._num_spheres = scene.num_spheres
+
+    def set_gloss_samples(self, roughness, table):
+        """rt_group_set_gloss_samples: Renderer.set_gloss_samples on every member."""
+        rough, tab, s, b = _gloss_table(roughness, table, getattr(self, "_num_spheres", None))
+        self._check_grp(self._L.rt_group_set_gloss_samples(self._grp, rough, tab, s, b), "rt_group_set_gloss_samples")
 
     def set_light_samples(self, offsets):
         """rt_group_set_light_samples: Renderer.set_light_samples on every member."""
@@ -959,6 +985,64 @@ def _light_table(offsets, num_lights):
             raise ValueError(f"light offsets are not [samples][{nl}][3]")
     flat = [x for row in rows for o in row for x in o]
     return (C.c_double * max(1, len(flat)))(*flat), len(rows)
+
+
+def gloss_pattern(n: int, bounces: int) -> list[list[tuple[float, float, float]]]:
+    """The n*n x bounces points of the unit ball that go with grid_pattern(n), as set_gloss_samples takes
+    them.  For sample s and bounce b: i = (s + 17*(b+1)) % (n*n), (x, y) point i of lens_pattern(n, 1.0),
+    h = (2*((7*i + 3) % (n*n)) + 1)/(n*n) - 1 in (-1, 1), z = h*sqrt(max(0, 1 - x*x - y*y)): the disk point
+    lifted to a height inside the ball above it.  The rotation by 17*(b+1) decorrelates the bounces from
+    each other and from the lens.  Only correctly rounded operations, in this order: ray_hip --gloss
+    computes the same doubles."""
+    if bounces < 1:
+        raise ValueError(f"gloss_pattern(bounces={bounces})")
+    import math
+
+    disk = lens_pattern(n, 1.0)
+    nn = n * n
+    pts = []
+    for s in range(nn):
+        row = []
+        for b in range(bounces):
+            i = (s + 17 * (b + 1)) % nn
+            x, y = disk[i]
+            h = (2 * ((7 * i + 3) % nn) + 1) / nn - 1.0
+            row.append((x, y, h * math.sqrt(max(0.0, 1.0 - x * x - y * y))))
+        pts.append(row)
+    return pts
+
+
+def scene_roughness(path_or_text: str) -> list[float]:
+    """Column 9 ("roughness") of a scene's accepted sphere records, in file order: entry i belongs to sphere i
+    of Scene.load / Scene.parse of the same argument (rt_scene_load_roughness / rt_scene_parse_roughness).  A
+    string with a newline, or one that names no file, is scene text."""
+    L = lib()
+    is_text = "\n" in path_or_text or not os.path.exists(path_or_text)
+    call, arg = ((L.rt_scene_parse_roughness, path_or_text.encode()) if is_text else
+                 (L.rt_scene_load_roughness, os.fsencode(path_or_text)))
+    n = C.c_int(0)
+    _check(call(arg, None, 0, C.byref(n)), "rt_scene_roughness")  # the sizing call
+    out = (C.c_double * max(1, n.value))()
+    _check(call(arg, out, n.value, C.byref(n)), "rt_scene_roughness")
+    return list(out[:n.value])
+
+
+def _gloss_table(roughness, table, num_spheres):
+    """(roughness, `gloss_xyz`, samples, bounces) of the gloss-table setters: `table` an [S][B][3] array-like
+    or None (the table is cleared), `roughness` num_spheres doubles.  num_spheres: the uploaded scene's, None
+    before an upload (the call then reports the missing scene)."""
+    if table is None:
+        return None, None, 0, 0
+    rough = [float(x) for x in roughness]
+    if num_spheres is not None and len(rough) != num_spheres:
+        raise ValueError(f"{len(rough)} roughness values for {num_spheres} spheres")
+    rows = [[tuple(float(x) for x in g) for g in row] for row in table]
+    nb = len(rows[0]) if rows else 0
+    for row in rows:
+        if len(row) != nb or any(len(g) != 3 for g in row):
+            raise ValueError(f"gloss points are not [samples][{nb}][3]")
+    flat = [x for row in rows for g in row for x in g]
+    return ((C.c_double * max(1, len(rough)))(*rough), (C.c_double * max(1, len(flat)))(*flat), len(rows), nb)
 
 
 def _lens_points(lens, samples: int):

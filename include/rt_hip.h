@@ -64,6 +64,12 @@
  *                                      reduction of the caller's per sample (the reference has point lights only,
  *                                      include/scene.h:94-120): per-sample light positions for the multi-sample
  *                                      entries, i.e. area lights with soft shadows
+ *   rt_set_gloss_samples / rt_group_set_gloss_samples, rt_scene_parse_roughness / rt_scene_load_roughness
+ *                                   <- (new) per reflection level one rt_trace_paths, one rt_trace_radiance and a
+ *                                      host pass that bends the reflection rays (the reference reflects as a
+ *                                      perfect mirror, src/main.cpp:45-48, and drops the scene files' roughness
+ *                                      column, include/scene_loader.h:66-70): glossy reflections for the
+ *                                      multi-sample entries
  *   launch_gpu_kernel, upload_lights_and_ambience (include/rt_hip_compat.h)
  *                                   <- the same symbols of src/kernel.cu:185-207, link-compatible
  *
@@ -105,7 +111,9 @@ extern "C" {
                                    thin-lens forms (rt_camera_lens_rays, rt_render_lens_samples_async,
                                    rt_render_lens_samples, rt_group_render_lens_samples) and the light table
                                    of the multi-sample entries (rt_set_light_samples,
-                                   rt_group_set_light_samples) */
+                                   rt_group_set_light_samples) and their gloss table (rt_set_gloss_samples,
+                                   rt_group_set_gloss_samples, rt_scene_parse_roughness,
+                                   rt_scene_load_roughness) */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -206,6 +214,14 @@ typedef struct rt_ctx rt_ctx;
 int rt_scene_load(const char *path, rt_scene *out, int verbose);
 int rt_scene_parse(const char *text, rt_scene *out, int verbose);
 void rt_scene_free(rt_scene *scene);
+/* Column 9 ("roughness") of every `sphere` record that rt_scene_parse / rt_scene_load accept, in file order:
+   the same reader, so out[i] belongs to scene.spheres[i] (rt_sphere has no field for it, as upstream's
+   loader drops it).  *n_out: the number of accepted records; at most `capacity` values are written, and out
+   may be NULL with capacity 0 (the sizing call).  Silent: the warnings are rt_scene_parse's to print.
+   Errors: a NULL text / path / n_out, a negative capacity or a NULL out with capacity > 0
+   RT_ERR_INVALID_ARG; a file that cannot be opened RT_ERR_IO.  What reads it: rt_set_gloss_samples. */
+int rt_scene_parse_roughness(const char *text, double *out, int capacity, int *n_out);
+int rt_scene_load_roughness(const char *path, double *out, int capacity, int *n_out);
 int rt_camera_from_scene(const rt_scene *scene, rt_camera *out);
 /* binary=0: P3 text byte-identical to write_ppm (src/main.cpp:69-91); binary=1: P6. */
 int rt_write_ppm(const char *path, const uint8_t *rgb, int width, int height, int binary);
@@ -720,6 +736,59 @@ int rt_render_lens_samples(rt_ctx *ctx, const rt_camera *cam, int width, int hei
    before any HIP call; no uploaded scene RT_ERR_NO_SCENE; an error leaves the previous table in force. */
 int rt_set_light_samples(rt_ctx *ctx, const double *light_xyz /* host, nullable */, int samples);
 
+/* ---- samples with glossy reflections ----------------------------------------
+   Replaces, per sample and reflection level, one rt_trace_paths with surfaces, one rt_trace_radiance with
+   fp64 colours through memory and a host pass that bends the reflection rays: a GLOSS TABLE, context state
+   set once, which gives every sample of the multi-sample entries its own perturbation of each reflection ray,
+   scaled by the roughness of the sphere it leaves.
+   roughness: HOST memory, num_spheres doubles, num_spheres the uploaded scene's (rt_scene_parse_roughness
+   gives a scene file's column).  gloss_xyz: HOST memory, samples * bounces * 3 doubles; the point of sample s
+   for bounce b is gloss_xyz[(s*bounces + b)*3 .. +2].  NULL clears the table (the other arguments are then
+   ignored).  With a table, `samples` is its sample count.
+   Which launches read it: while a table is set, every RESOLVING radiance launch --
+   rt_trace_radiance_resolve[_async], rt_render_samples (through its resolve launches),
+   rt_render_samples_async, rt_render_lens_samples[_async], rt_group_render_samples and
+   rt_group_render_lens_samples.  For sample s (ray p*samples + s of pixel p), at a level k (the camera ray's
+   hit is level 0) whose hit on sphere i spawns a reflection ray -- the decision itself is unchanged --, with
+   d the incoming direction and nrm the normal, all in fp64 without contraction:
+     rd  = d - (nrm*2.0)*dot(d, nrm)                   the mirror direction, unnormalised, as before
+     g   = gloss_xyz[(s*bounces + k)*3 .. +2]          bounce index == level index
+     rp  = rd + g*roughness[i]                         the product rounded, then the sum
+     use = k < bounces && roughness[i] != 0.0 && dot(rp, nrm) * dot(rd, nrm) > 0.0
+     d'  = normalized(use ? rp : rd)                   from hp + nrm*EPSILON as before
+   Roughness 0 is always a mirror, and so is every bounce k >= bounces; the table is not read for either.  A
+   perturbed direction on the wrong side of the surface or in its tangent plane, and every NaN (in g, in the
+   roughness, or made of an infinity: 0 * inf, inf - inf), fail the comparison and fall back to the mirror
+   direction.  Any double is allowed and nothing is an error: an infinite g or roughness that passes the
+   comparison as written gives a direction that is not finite, which hits nothing, as a caller's own ray of
+   that kind does.
+   The closest hit, the shadow rays, the Phong terms, the stack, the composite, the resolve rule, the
+   quantiser and the formats are untouched, and so are the acceleration rule per segment and the counters:
+   segments, hits and shadow_rays count what is traced.  A light table (rt_set_light_samples) composes: one
+   sample sees moved lights and bent reflections.
+   What never reads it: rt_trace_radiance[_async] and the ray and path queries (no sample index), and every
+   render (rt_render*, the tile renders, rt_set_antialias, rt_group_render, rt_group_render_frames).  Without a
+   table every call writes exactly what it wrote before this entry existed.
+   Sample-count mismatch: the light table's rule.  A resolving call whose `samples` differs from the gloss
+   table's is RT_ERR_INVALID_ARG, tested next to the light table's check, before any HIP call (also for
+   n == 0 or no rows); on a group rt_group_last_error names the two counts.  With both tables set each must
+   match.
+   Synchronous: waits for the context's stream (work in flight may read the table being replaced), uploads
+   samples * bounces points of 24 bytes and num_spheres doubles, and returns; both host arrays are free on
+   return.  The _async entries gain no launch, buffer or wait: they pass two pointers and an int.
+   Lifetime: rt_upload_scene clears the table (the sphere count may change), rt_destroy frees it.  A scene
+   without spheres accepts the call and stores an empty roughness array: the launches write what they write
+   without a table, and the sample-count check still holds.
+   Stats: unchanged rules, the same counters and events, the same 32-bit per-lane counter check of the
+   fused launches (no trip, sample, depth or light count changes).
+   Errors: NULL ctx, or a non-NULL gloss_xyz with a NULL roughness, samples outside 1..RT_MAX_SAMPLES or
+   bounces outside 1..RT_MAX_GLOSS_BOUNCES, RT_ERR_INVALID_ARG before any HIP call; no uploaded scene
+   RT_ERR_NO_SCENE; an error leaves the previous table in force. */
+#define RT_MAX_GLOSS_BOUNCES (RT_MAX_DEPTH - 1)
+int rt_set_gloss_samples(rt_ctx *ctx, const double *roughness /* host, num_spheres doubles */,
+                         const double *gloss_xyz /* host, samples*bounces*3 doubles; NULL clears */, int samples,
+                         int bounces);
+
 /* ---- device group: one image row-sharded over several contexts ------------
  * Replaces render_multi in csrc/ray_hip.cpp -- G contexts, their
  * streams and shard buffers, ncclGather to device 0, rt_unpermute_rows -- with
@@ -798,6 +867,13 @@ int  rt_group_render_lens_samples(rt_group *grp, const rt_camera *cam, int width
    rt_group_upload_scene clears the table on every member.  Errors: rt_set_light_samples', with the cause
    in rt_group_last_error; RT_ERR_NO_SCENE without rt_group_upload_scene. */
 int  rt_group_set_light_samples(rt_group *grp, const double *light_xyz /* host, nullable */, int samples);
+
+/* rt_set_gloss_samples on every member ("samples with glossy reflections" above): the two group sample
+   renders then bend sample s's reflection rays, byte for byte what the single-context calls write.
+   rt_group_upload_scene clears the table on every member.  Errors: rt_set_gloss_samples', with the cause in
+   rt_group_last_error; RT_ERR_NO_SCENE without rt_group_upload_scene. */
+int  rt_group_set_gloss_samples(rt_group *grp, const double *roughness, const double *gloss_xyz /* nullable */,
+                                int samples, int bounces);
 
 #ifdef __cplusplus
 }
