@@ -118,7 +118,13 @@ struct RenderArgs {
   int rows_dword;                 // kStackMerge: every 8-pixel tile row starts dword aligned (flush_tile)
   int defer_level;                // kStackMerge: rays of this reflection level and deeper are deferred
   int xcd_frames;                 // multi-frame launches: every frame of a tile group on one XCD (render_kernel)
+  const double *dirs;             // kStackMerge: the launch's ray table (ray_table_kernel), or nullptr: rays formed inline
 };
+// The ray table: per tile (its unpermuted index) the planes x, y, z of the 64
+// lanes' camera-ray directions, 512 B each -- a wave's load of one plane is one
+// contiguous run at a scalar tile base plus the lane's offset.
+constexpr int kRayTileDoubles = 3 * 64;
+constexpr size_t kRayTileBytes = kRayTileDoubles * sizeof(double);
 // the whole struct is the kernel's argument block (kernarg segment, at most 4 KiB)
 static_assert(sizeof(RenderArgs) <= 4096, "RenderArgs exceeds the kernel-argument segment");
 
@@ -937,8 +943,15 @@ __device__ __forceinline__ void merge_tiles(const SphGeo *__restrict__ g, const 
         const bool in_img = in_tile && y < H;
         const int j = H - 1 - (int)(in_img ? y : 0);  // reference row (main.cpp:74)
         const Cam &cam = kernarg_cam(frame);
-        const D3 dir = camera_dir(cam, (double)x, (double)j, W, H);
-        d = renormalized(normalized(dir));
+        // the launch's ray table (the frames share the orientation, the image and the rows): this tile's
+        // directions as ray_table_kernel formed them, with these same expressions
+        if (const double *dirs = kernarg_late<true, offsetof(RenderArgs, dirs)>(a.dirs)) {
+          const double *tb = dirs + (size_t)tile * kRayTileDoubles;
+          d = mk(tb[lane], tb[64 + lane], tb[128 + lane]);
+        } else {
+          const D3 dir = camera_dir(cam, (double)x, (double)j, W, H);
+          d = renormalized(normalized(dir));
+        }
         o = mk(cam.px, cam.py, cam.pz);
         pix = (unsigned)(k * W + x);
         lidx = next * 64 + lane;
@@ -1478,6 +1491,40 @@ __global__ __launch_bounds__(64, RT_MIN_WAVES_PER_EU) void render_deferred_walk(
   flush_counts(kernarg_late<true, offsetof(RenderArgs, counters)>(a.counters), sums, work);
 }
 
+// The build pass of a launch's ray table (RenderArgs::dirs): a wave per 8x8
+// tile, a lane per pixel, with merge_tiles' own expressions for the pixel, its
+// image row and its ray (camera.h:17-25, main.cpp:151-154), so the bits are
+// the ones a tile pass would form; a padding lane (x >= W, a row past the
+// launch's or the image's) holds what the inline code forms for it.
+struct RayBuild {
+  Cam cam;  // the orientation and scale (the position is not read)
+  int W, H;
+  Rows rows;
+  int ntx, ntiles;
+  double *out;  // [ntiles][kRayTileDoubles]
+};
+__global__ __launch_bounds__(256) void ray_table_kernel(const RayBuild b) {
+  const int lane = (int)(threadIdx.x & 63);
+  const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tile >= b.ntiles) return;
+  const int tx = (int)(tile % b.ntx), ty = (int)(tile / b.ntx);
+  const Rows &rows = b.rows;
+  const int W = b.W, H = b.H;
+  const int x = tx * 8 + (lane & 7);
+  const int k = ty * 8 + (lane >> 3);
+  const bool in_tile = x < W && k < rows.count;
+  const long long y = (long long)(k / rows.band) * rows.band * rows.stride +
+                      (long long)rows.first * rows.band + (k % rows.band);
+  const bool in_img = in_tile && y < H;
+  const int j = H - 1 - (int)(in_img ? y : 0);
+  const D3 dir = camera_dir(b.cam, (double)x, (double)j, W, H);
+  const D3 d = renormalized(normalized(dir));
+  double *tb = b.out + (size_t)tile * kRayTileDoubles;
+  tb[lane] = d.x;
+  tb[64 + lane] = d.y;
+  tb[128 + lane] = d.z;
+}
+
 // Reassemble rank-major shards into PPM row order (one workgroup per row).
 __global__ __launch_bounds__(kBlock) void unpermute_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                                                            int W, int H, int band, int G, int R) {
@@ -1769,6 +1816,20 @@ struct CamGrids {
   int tab_next = 0;
 };
 
+// The ray table (RenderArgs::dirs, ray_table_kernel) and what it was built for; it does not depend on the
+// scene, so an upload leaves it.
+struct RayTable {
+  DevBuf<double> buf;
+  RayKey key{}, seen{};  // the table's key; the previous merged launch's key
+  bool valid = false, seen_valid = false;
+  // rt_set_ray_table: the policy's mode (rt_sched.h ray_table_policy: 0 never, 1 launches of two frames or
+  // more, a kept table's key and a key's second one-frame launch, 2 every launch of one key) and the bytes a
+  // table may take (-1: kRayBudgetBytes)
+  int mode = 1;
+  long long budget = -1;
+  size_t bytes() const { return buf.bytes(); }
+};
+
 // The cached launch order of the tiles (tile_perm) and the view it was built for.
 struct TileOrder {
   SchedView view{};
@@ -1813,6 +1874,10 @@ struct BuildInfo {
   unsigned long long cg_builds = 0, perm_builds = 0;
   double cg_build_ms = 0.0, perm_build_ms = 0.0, upload_ms = 0.0, sg_build_ms = 0.0, ug_build_ms = 0.0;
   double bvh_build_ms = 0.0, lg_build_ms = 0.0;  // rt_upload_scene's host builds
+  // rt_get_ray_table_info: the ray table's builds, and whether the most recent launch read one
+  bool rays_last = false;
+  unsigned long long rays_builds = 0;
+  double rays_build_ms = 0.0;
 };
 
 // The launch state of one family of caller-ray queries.  rt_ctx keeps one per
@@ -1857,6 +1922,7 @@ struct rt_ctx {
   Scene scene;
   unsigned long long scene_gen = 0;  // counts the uploads: what the caches below were built for
   CamGrids cg;
+  RayTable rays;
   TileOrder order;
   Counters ctr;
   LaunchTiming timing;
@@ -2182,6 +2248,78 @@ int cam_grid_enqueue(rt_ctx *c, const CgPlan &p, CgArgs &out) {
     c->info.cg_build_ms += ms_since(t0);
   }
   out = CgArgs{c->cg.count.get(), c->cg.ent.get(), p.N, 1, p.ngrid > 1 ? 1 : 0, p.ngrid};
+  return RT_OK;
+}
+
+// The ray table of this launch (rt_sched.h ray_table_policy; plan.use = false: the launch forms its rays
+// inline as before).  Like the camera grids: the host part -- policy and buffer, which may wait for the
+// stream -- runs before the launch's start event, ray_table_enqueue puts the build pass on the stream ahead
+// of the render kernel.  The table takes at most kRayBudgetBytes and half the device's free memory; past
+// that, or when the allocation fails, the launch runs inline (RT_OK).
+constexpr size_t kRayBudgetBytes = size_t(1) << 30;
+struct RayPlan {
+  bool use = false, build = false;
+  RayKey key{};
+  int ntx = 0;
+  long long ntiles = 0;
+};
+Cam to_cam(const rt_camera &cm);
+RayKey ray_key(const rt_camera &cm, const LaunchReq &q) {
+  RayKey k{};
+  std::memcpy(k.orient, cm.forward, 3 * sizeof(double));
+  std::memcpy(k.orient + 3, cm.right, 3 * sizeof(double));
+  std::memcpy(k.orient + 6, cm.up, 3 * sizeof(double));
+  k.orient[9] = cm.scale;
+  k.W = q.W, k.H = q.H;
+  k.band = q.rows.band, k.first = q.rows.first, k.stride = q.rows.stride, k.count = q.rows.count;
+  return k;
+}
+void ray_table_prepare(rt_ctx *c, const LaunchReq &q, int ntx, long long ntiles, RayPlan &p) {
+  p = RayPlan{};
+  RayTable &t = c->rays;
+  const RayKey key = ray_key(q.cams[0], q);
+  bool uniform = true;
+  for (int f = 1; f < q.nframes; f++) uniform = uniform && ray_key_equal(ray_key(q.cams[f], q), key);
+  const RayUse use = ray_table_policy(t.mode, uniform, q.nframes, key, t.valid ? &t.key : nullptr,
+                                      t.seen_valid ? &t.seen : nullptr);
+  t.seen = key;
+  t.seen_valid = uniform;
+  if (use == kRayInline) return;
+  p.key = key, p.ntx = ntx, p.ntiles = ntiles;
+  if (use == kRayReuse) {
+    p.use = true;
+    return;
+  }
+  const size_t total = (size_t)ntiles * kRayTileBytes;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+    (void)hipGetLastError();
+    free_b = 0;
+  }
+  const size_t limit = t.budget >= 0 ? (size_t)t.budget : kRayBudgetBytes;
+  // what the table holds now counts as available: growing frees it first
+  if (total > limit || total > (free_b + t.bytes()) / 2) return;
+  t.valid = false;  // from here the buffer changes: the kept table is gone whatever happens
+  if (!grow_soft(c, t.buf, total)) return;  // no memory for the table: this launch forms its rays inline
+  p.use = p.build = true;
+}
+
+int ray_table_enqueue(rt_ctx *c, const LaunchReq &q, const RayPlan &p, RenderArgs &ra) {
+  ra.dirs = nullptr;
+  if (!p.use) return RT_OK;
+  RayTable &t = c->rays;
+  if (p.build) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const RayBuild b{to_cam(q.cams[0]), q.W, q.H, q.rows, p.ntx, (int)p.ntiles, t.buf.get()};
+    hipLaunchKernelGGL(ray_table_kernel, dim3((unsigned)((p.ntiles + 3) / 4)), dim3(256), 0, c->stream, b);
+    RT_TRY(c, hipGetLastError());
+    // valid for later launches only once its pass is on the stream
+    t.key = p.key;
+    t.valid = true;
+    c->info.rays_builds++;
+    c->info.rays_build_ms += ms_since(t0);
+  }
+  ra.dirs = t.buf.get();
   return RT_OK;
 }
 
@@ -2859,7 +2997,7 @@ RenderArgs render_args(const rt_ctx *c, const LaunchReq &q, const Cam &cam, cons
 // What a launch put on the stream, for enqueue's bookkeeping: a render kernel (it zeroes
 // the other counter half), whether it used camera grids (of cg_n cells) / the behind grid.
 struct Launched {
-  bool kernel = false, cg = false, ug = false;
+  bool kernel = false, cg = false, ug = false, rays = false;
   int cg_n = 0;
 };
 
@@ -2927,14 +3065,18 @@ int launch_tiles(rt_ctx *c, const LaunchReq &q, KernelSel sel, const Cam &cam, B
   // render kernel are part of the launch
   CgPlan plan;
   if (sel.fast && sel.cull && (rc = cam_grid_prepare(c, q, plan)) != RT_OK) return rc;
+  // the ray table's host part likewise (merged launches of whole images; rt_render_tiles keeps its inline rays)
+  RayPlan rays;
+  if (merge && !q.tiles) ray_table_prepare(c, q, ntx, ntiles, rays);
   RT_TRY(c, mark_start(c));
   if ((rc = cam_grid_enqueue(c, plan, ra.cg)) != RT_OK) return rc;
+  if ((rc = ray_table_enqueue(c, q, rays, ra)) != RT_OK) return rc;
   if (sel.fast && sel.cull && scn.sg_ok)
     ra.sg = SgArgs{scn.sg_start.get(), scn.sg_ent.get(), scn.sg_rho2.get(), scn.sg_n, 1,
                    scn.sg_nstart,      scn.sg_nent, scn.nsph};
   void *args[] = {&ra};
   RT_TRY(c, hipLaunchKernel(kf, grid, dim3(64 * kWg), args, lds, c->stream));
-  did = Launched{true, ra.cg.on != 0, bv.ug.on != 0, ra.cg.on ? ra.cg.N : 0};
+  did = Launched{true, ra.cg.on != 0, bv.ug.on != 0, ra.dirs != nullptr, ra.cg.on ? ra.cg.N : 0};
   if (ra.dq_cap > 0) {  // 48 one-wave workgroups per shard segment
     // the walk kernel where every closest hit walks the BVH anyway (large
     // scenes: synth10k 12.2 -> 11.0 ms per 8-frame launch); small scenes keep
@@ -3017,6 +3159,7 @@ int enqueue(rt_ctx *c, const LaunchReq &q) {
   }
   c->info.cg_last = did.cg;
   c->info.cg_last_n = did.cg_n;
+  c->info.rays_last = did.rays;
   c->timing.launches++;
   c->scene.launches++;
   return RT_OK;  // the counters are read back by rt_render_stats, after the stream drains
@@ -4233,9 +4376,26 @@ int rt_get_info(rt_ctx *c, rt_info *out) {
   out->bvh_build_ms = c->info.bvh_build_ms;
   out->light_grid_build_ms = c->info.lg_build_ms;
   out->scratch_bytes = (uint64_t)(c->gstack.bytes() + c->dq.bytes() + c->homes.bytes() + c->home_bits.bytes() +
-                                  c->cg.bytes() + c->order.perm.bytes());
+                                  c->cg.bytes() + c->order.perm.bytes() + c->rays.bytes());
   out->shadow_line_bounded = c->scene.lg_off_free ? 1 : 0;
   out->reserved0 = 0;
+  return RT_OK;
+}
+
+int rt_set_ray_table(rt_ctx *c, int mode, int64_t budget_bytes) {
+  if (!c || mode < 0 || mode > 2) return RT_ERR_INVALID_ARG;
+  c->rays.mode = mode;
+  c->rays.budget = budget_bytes < 0 ? -1 : budget_bytes;
+  return RT_OK;
+}
+
+int rt_get_ray_table_info(rt_ctx *c, rt_ray_table_info *out) {
+  if (!c || !out) return RT_ERR_INVALID_ARG;
+  *out = rt_ray_table_info{};
+  out->builds = c->info.rays_builds;
+  out->used_last = c->info.rays_last ? 1 : 0;
+  out->bytes = (uint64_t)c->rays.bytes();
+  out->build_ms = c->info.rays_build_ms;
   return RT_OK;
 }
 

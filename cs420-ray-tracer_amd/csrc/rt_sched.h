@@ -12,6 +12,7 @@
 // (longest-processing-time-first list scheduling).  Only the order of the
 // launch changes; every pixel is traced exactly as before.
 #pragma once
+#include <cstring>
 #include <vector>
 
 namespace rtk {
@@ -35,5 +36,40 @@ struct SchedView {
 constexpr int kSchedClasses = 4;  // 0 .. 3 reflective spheres over a tile (capped)
 void tile_order(const SchedView &v, const std::vector<SchedSphere> &refl, std::vector<int> &perm,
                 long long *class_count = nullptr);
+
+// The ray table of a launch (rt_kernel.hip ray_table_prepare): the camera
+// rays' directions depend only on the camera's
+// orientation, the image and the launch's rows -- not on the scene, the
+// camera's position or the frame -- so a launch whose frames share them forms
+// them once, in a pass ahead of the render kernel, and keeps them for the
+// launches that follow.  This is what a table was formed for, compared by
+// memcmp as the camera grid compares positions.
+struct RayKey {
+  double orient[10];               // forward, right, up, scale (Cam's)
+  int W, H;
+  int band, first, stride, count;  // Rows
+  int pad[2];                      // 0 (no padding bytes: the struct is compared whole)
+};
+static_assert(sizeof(RayKey) == 10 * sizeof(double) + 8 * sizeof(int), "RayKey has padding");
+inline bool ray_key_equal(const RayKey &a, const RayKey &b) { return std::memcmp(&a, &b, sizeof(RayKey)) == 0; }
+
+// What a launch does about the table.  mode: rt_set_ray_table's (0 never, 1 the
+// policy below, 2 every launch with one key).  uniform: every frame of the
+// launch has `key`.  kept: the key of the table the context holds, prev: the
+// key of the previous launch (nullptr: none, or its frames had several).
+//  - frames of differing keys, or mode 0: the rays are formed inline;
+//  - the kept table has this key: it is used as it is;
+//  - else a launch of two frames or more builds one, and so does a one-frame
+//    launch whose key the previous launch had too (the camera grid's
+//    second-sighting rule: the build pass costs a first frame more than
+//    forming its rays inline), or any launch with mode 2.
+enum RayUse { kRayInline = 0, kRayReuse = 1, kRayBuild = 2 };
+inline RayUse ray_table_policy(int mode, bool uniform, int nframes, const RayKey &key, const RayKey *kept,
+                               const RayKey *prev) {
+  if (mode <= 0 || !uniform || nframes < 1) return kRayInline;
+  if (kept && ray_key_equal(key, *kept)) return kRayReuse;
+  if (mode >= 2 || nframes >= 2 || (prev && ray_key_equal(key, *prev))) return kRayBuild;
+  return kRayInline;
+}
 
 }  // namespace rtk

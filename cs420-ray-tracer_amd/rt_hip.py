@@ -95,6 +95,14 @@ class rt_info(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class rt_ray_table_info(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("used_last", C.c_int32), ("reserved0", C.c_int32), ("bytes", C.c_uint64),
+                ("build_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class rt_tile(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -223,6 +231,8 @@ SIGNATURES = {
                                   C.c_int, _P]),
     "rt_set_antialias": (C.c_int, [_P, C.c_int]),
     "rt_get_info": (C.c_int, [_P, C.POINTER(rt_info)]),
+    "rt_get_ray_table_info": (C.c_int, [_P, C.POINTER(rt_ray_table_info)]),
+    "rt_set_ray_table": (C.c_int, [_P, C.c_int, C.c_int64]),
     "rt_trace_rays_async": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P]),
     "rt_trace_rays": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_int, C.POINTER(rt_query_stats)]),
     "rt_trace_stats": (C.c_int, [_P, C.POINTER(rt_query_stats)]),
@@ -545,6 +555,17 @@ class Renderer:
         inf = rt_info()
         _check(self._L.rt_get_info(self._ctx, C.byref(inf)), "rt_get_info", self._ctx, L=self._L)
         return inf
+
+    def ray_table_info(self) -> rt_ray_table_info:
+        """rt_get_ray_table_info: the ray table's builds, and whether the most recent launch read one."""
+        inf = rt_ray_table_info()
+        _check(self._L.rt_get_ray_table_info(self._ctx, C.byref(inf)), "rt_get_ray_table_info", self._ctx, L=self._L)
+        return inf
+
+    def set_ray_table(self, mode: int = 1, budget_bytes: int = -1):
+        """rt_set_ray_table: 0 never a ray table, 1 the default rule, 2 also for a first one-frame launch; the
+        bytes a table may take (negative: the default)."""
+        _check(self._L.rt_set_ray_table(self._ctx, mode, budget_bytes), "rt_set_ray_table", self._ctx, L=self._L)
 
     def kernel_times(self, max_n: int = 256) -> list[float]:
         """Per-launch kernel durations (ms) since the previous call (syncs the stream)."""

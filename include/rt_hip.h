@@ -34,6 +34,9 @@
  *   rt_set_antialias                <- the `-a` flag of ray_gpu, src/main_gpu.cu:249-333, 363-370
  *   rt_get_info                     <- (new) the host-side builds the render calls made (camera grid,
  *                                      tile launch order) and their cost
+ *   rt_get_ray_table_info / rt_set_ray_table
+ *                                   <- (new) the ray table of the render launches: Camera::get_ray
+ *                                      include/camera.h:17-25 formed once per orientation, not once per frame
  *   rt_trace_rays / rt_trace_rays_async / rt_trace_stats
  *                                   <- Scene::find_intersection include/scene.h:41-61 (closest hit) and the any-hit
  *                                      half of Scene::in_shadow include/scene.h:65-86 (occlusion), for rays the
@@ -113,7 +116,7 @@ extern "C" {
                                    of the multi-sample entries (rt_set_light_samples,
                                    rt_group_set_light_samples) and their gloss table (rt_set_gloss_samples,
                                    rt_group_set_gloss_samples, rt_scene_parse_roughness,
-                                   rt_scene_load_roughness) */
+                                   rt_scene_load_roughness) and rt_get_ray_table_info, rt_set_ray_table */
 /* Longest reflection chain the GPU path keeps per pixel (depth <= RT_MAX_DEPTH). */
 #define RT_MAX_DEPTH 64
 
@@ -362,12 +365,38 @@ typedef struct rt_info {
     double bvh_build_ms;         /* host wall time of the BVH build and upload, part of upload_ms */
     double light_grid_build_ms;  /* host wall time of the light grids' build and upload, part of upload_ms */
     uint64_t scratch_bytes;      /* device scratch the context holds for its launches: reflection stacks (stack
-                                    homes / per-pixel stack), the deferred queue, the camera grids, the tile order */
+                                    homes / per-pixel stack), the deferred queue, the camera grids, the tile order,
+                                    the ray table */
     int32_t shadow_line_bounded; /* 1: the scene's bound keeps every shadow line within its light grid's margin, so
                                     the per-ray check is skipped (rt_device.h shadow_cells off_free); 0: checked */
     int32_t reserved0;
 } rt_info;
 int rt_get_info(rt_ctx *ctx, rt_info *out);
+
+/* The ray table of the whole-image render launches (rt_render, rt_render_async, rt_render_frames_async and
+ * the rt_group renders; not rt_render_tile(s), the antialias mode or the query and sample families).  A
+ * camera ray's direction depends only on the camera's orientation (forward, right, up, scale), the image
+ * size and the launch's rows -- not on the scene, the camera's position or the frame -- so a launch whose
+ * frames share them forms the directions once, in a device pass ahead of
+ * the render kernel and inside the launch's timing, 24 bytes per launch pixel, and the context keeps the
+ * table until a launch with another orientation, size or rows replaces it.  A table is
+ * built by a launch of two frames or more and by a one-frame launch that repeats the previous launch's
+ * orientation, size and rows; any other launch forms its rays in the render kernel, as does one whose
+ * table would take more than 1 GiB or half the free device memory.  The pixels are the same bytes either
+ * way.  rt_set_ray_table(ctx, mode, budget_bytes) sets the rule for the context's later launches: mode 0
+ * never uses a table, 1 is the rule above (default), 2 builds one for a first one-frame launch too;
+ * budget_bytes is the most a table may take (negative: the default of 1 GiB; 0: every launch forms its rays
+ * in the kernel).  It is a call, not an environment variable: the library reads RT_HIP_LDS_SCENE and
+ * RT_HIP_CAM_GRID from the environment and nothing else.  rt_info.scratch_bytes counts the table. */
+typedef struct rt_ray_table_info {
+    uint64_t builds;    /* tables built since rt_create */
+    int32_t used_last;  /* 1: the most recent launch read its camera rays from a table */
+    int32_t reserved0;
+    uint64_t bytes;     /* device memory the context holds for the table */
+    double build_ms;    /* host wall time of enqueueing those builds */
+} rt_ray_table_info;
+int rt_get_ray_table_info(rt_ctx *ctx, rt_ray_table_info *out);
+int rt_set_ray_table(rt_ctx *ctx, int mode, int64_t budget_bytes); /* RT_ERR_INVALID_ARG: no context, mode not 0..2 */
 
 /* Reassemble G shards gathered rank-major ([G][rows_per_rank][W][3], rank r
  * rendered with rt_rows{band, r, G, rows_per_rank}) into a PPM-ordered
